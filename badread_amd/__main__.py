@@ -16,7 +16,7 @@ import sys
 # A hardware queue per HIP stream of every batch in flight (8 batches x up to 3 streams): HIP's default of 4 queues
 # serialises kernels of different streams.  Must be in the environment before the HIP runtime starts (the first torch.cuda
 # call), which is why it is set here, at the top of the command line's module, and not where the streams are created.
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '40')
+os.environ.setdefault('GPU_MAX_HW_QUEUES', '32')
 
 from . import settings
 from .misc import str_is_dna_sequence, str_is_int

@@ -2,7 +2,7 @@
 """
 bench.py -- simulated bases per second of the HIP hot path on N MI355X (one process per GPU).
 
-    python bench.py --gpus N --steps K --warmup W [--workload human|hifi|kpn]
+    python bench.py --gpus N --steps K --warmup W [--workload human|hifi|kpn] [--dump-outputs DIR] [--full]
 
 With N > 1 and no WORLD_SIZE in the environment the script re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one rank per GPU; a
@@ -35,7 +35,12 @@ reference, engines and arenas, model tables, priming).  The line then carries `f
 batch, the slowest rank), `loop_s`, `value` = job bases / (fixed + loop), `value_loop`, and `projected_wall_s` for 1 / 2 / 4 / 8
 ranks from the measured fixed cost and loop -- what a scaling box would see, since the fixed cost does not shrink with N.
 
-The JSON line carries
+A plain run sets up, warms up, times the K steps and prints the line: `value` (simulated bases/s, all ranks), `ms_per_step` (wall
+time of one timed step), the stage times the library records anyway, the host's share.  `--dump-outputs DIR` then writes what the
+last timed step computed (dump_outputs(): per-read statistics, a seeded sample of whole FASTQ records, per-batch byte sums) as
+.npy files; the inputs are seeded, so two builds run with the same arguments compare output for output.
+
+With `--full` the kernels are timed launch by launch (HIP events; extra synchronisation inside every batch) and the JSON line carries
   roofline       the kernel with the largest summed launch time in this very run (per-kernel HIP events around
                  every launch, on the stream the kernel is launched on: brx_last_kernel_stats), HBM bound, algorithmic
                  bytes = 2.26 B per simulated base x the bases that kernel handled / its launches
@@ -49,7 +54,7 @@ import time as _time
 T_PROCESS = _time.perf_counter()       # --scaling strong: the clock of a rank starts here, before torch is imported
 import argparse
 import os as _os
-_os.environ.setdefault('GPU_MAX_HW_QUEUES', '40')      # a hardware queue per stream of every in-flight batch (HIP's default of 4 serialises them)
+_os.environ.setdefault('GPU_MAX_HW_QUEUES', '32')      # a hardware queue per stream of every in-flight batch (HIP's default of 4 serialises them)
 import json
 import os
 import sys
@@ -285,6 +290,63 @@ def valu_per_base(workload):
         return None
 
 
+DUMP_STATS_BYTES = 44 << 20          # --dump-outputs: per-read statistics (float64), all reads of the last step up to this size
+DUMP_FASTQ_BYTES = 4 << 20           # FASTQ bytes of a seeded sample of whole records (one float32 per byte: 16 MiB)
+
+
+def dump_outputs(out_dir, last):
+    """--dump-outputs: what the timed path handed its caller in the last step, as DIR/<name>.npy (float64 / float32, < 64 MB).
+    `last` = [(first read, FASTQ bytes, stats)] of the device batches of that step (one per batch in flight), in read order.
+      read_index, stats_<field>   every read of the step (a seeded sample of them if they exceed DUMP_STATS_BYTES)
+      fastq_sample_bytes          the records of a seeded sample of reads, concatenated (fastq_sample_read_index, fastq_sample_rec_len)
+      fastq_batch_bytes, fastq_batch_byte_sum   length and byte sum of each batch's whole FASTQ output"""
+    import torch
+    last = sorted(last, key=lambda t: t[0])
+    stats = np.concatenate([st for _, _, st in last])
+    index = np.concatenate([first + np.arange(len(st), dtype=np.int64) for first, _, st in last])
+    batch = np.concatenate([np.full(len(st), b, dtype=np.int64) for b, (_, _, st) in enumerate(last)])
+    fields = stats.dtype.names
+    rng = np.random.default_rng(SEED)
+    n = len(stats)
+    keep = np.arange(n)
+    per_read = 8 * (len(fields) + 1)
+    if n * per_read > DUMP_STATS_BYTES:
+        keep = np.sort(rng.choice(n, DUMP_STATS_BYTES // per_read, replace=False))
+    arrays = {'read_index': index[keep].astype(np.float64)}
+    for f in fields:
+        arrays['stats_' + f] = stats[f][keep].astype(np.float64)
+    picked, total = [], 0
+    for r in rng.permutation(n):
+        size = int(stats['rec_len'][r])
+        if total + size > DUMP_FASTQ_BYTES:
+            break
+        picked.append(int(r)); total += size
+    picked.sort()
+    parts = []
+    for r in picked:
+        out = last[batch[r]][1]
+        lo = int(stats['rec_off'][r])
+        part = out[lo: lo + int(stats['rec_len'][r])]
+        parts.append(part.cpu().numpy() if isinstance(part, torch.Tensor) else np.asarray(part, dtype=np.uint8))
+    arrays['fastq_sample_bytes'] = (np.concatenate(parts) if parts else np.zeros(0, np.uint8)).astype(np.float32)
+    arrays['fastq_sample_read_index'] = index[picked].astype(np.float64)
+    arrays['fastq_sample_rec_len'] = stats['rec_len'][picked].astype(np.float64)
+    sizes, sums = [], []
+    for _, out, _ in last:
+        sizes.append(float(len(out)))
+        if isinstance(out, torch.Tensor):
+            sums.append(float(out.sum(dtype=torch.int64).item()))         # exact: < 2^53 for any batch that fits a device
+        else:
+            sums.append(float(np.asarray(out, dtype=np.uint8).sum(dtype=np.int64)))
+    arrays['fastq_batch_bytes'] = np.array(sizes, dtype=np.float64)
+    arrays['fastq_batch_byte_sum'] = np.array(sums, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), arr)
+    print(f'[bench] --dump-outputs: {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values()) / 2 ** 20:.1f} MiB in {out_dir}',
+          file=sys.stderr, flush=True)
+
+
 # ------------------------------------------------------------------------------------------------ launch
 def respawn_under_torchrun(args_list, n):
     """`python bench.py --gpus N` without a launcher: start N ranks of this script (one per GPU) and wait."""
@@ -313,7 +375,7 @@ def main():
     ap.add_argument('--streams', type=int, default=6,
                     help='device batches in flight per GPU (one context + HIP stream + host thread each): the slowest '
                          'read of one device batch overlaps the bulk of the others')
-    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='seconds each host core runs the cpu_baseline leg (0 = skip)')
+    ap.add_argument('--cpu-seconds', type=float, default=12.0, help='seconds each host core runs the cpu_baseline leg of --full (0 = skip)')
     ap.add_argument('--d2h', action='store_true', help='also run the same amount of work through the CLI driver (PCIe + host output stage): value_incl_d2h, value_incl_gzip')
     ap.add_argument('--d2h-legs', default='devnull_cold,devnull,gzip_device,gzip1', help='which --d2h legs to run (comma separated)')
     ap.add_argument('--ref-dir', default=default_ref_dir(), help='where the synthetic reference FASTA and its packed sidecar live')
@@ -322,6 +384,13 @@ def main():
                     help='weak (default; the driver\'s line): fixed work per GPU, inputs resident before the clock.  strong: the fixed --quantity job '
                          'split over the ranks, every rank\'s start-up inside the clock (fixed_cost_s, loop_s, projected_wall_s); --steps / --warmup are ignored')
     ap.add_argument('--quantity', type=float, default=30.0, help='--scaling strong: depth of the job (x the reference; 30 = the metric\'s job)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: per-kernel launch timing (kernels_per_device_batch, roofline, '
+                         'roofline_alu) and the CPU baseline leg (--cpu-seconds per host core).  Off: set up, warm up, time the steps, '
+                         'write --dump-outputs, print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (read statistics, a seeded sample of the FASTQ '
+                         'records, per-batch byte counts and sums) as DIR/<name>.npy in float64 / float32, at most 64 MB in all')
     ap.add_argument('--cpu-engine', action='store_true',
                     help='DRY RUN of the launch / sharding / reporting logic on the CPU checker engine over gloo (tests only: '
                          'the line it prints is marked invalid and measures nothing)')
@@ -413,7 +482,8 @@ def main():
                 torch.cuda.set_device(local)
                 if i:
                     engines[i] = first.clone()
-                engines[i].set_kernel_timing(True)
+                if args.full:                              # events around every launch: the per-kernel figures of --full
+                    engines[i].set_kernel_timing(True)
                 with torch.cuda.stream(streams[i]):        # prime the context (lazy module load, buffers) -- not a step
                     engines[i].simulate_batch_device(SEED, 2 ** 40, 64, expected_bytes=int(R * first.expected_record_bytes() * 1.05))
                     streams[i].synchronize()
@@ -433,12 +503,13 @@ def main():
     n_job = max(1, int(np.ceil(args.quantity * float(pref.n_bases) / (R * mean_len)))) if strong else 0
 
     def run_one(e, index):
+        """(first read, FASTQ bytes, stats) of device batch `index`; the bytes stay on the device until the engine's next batch."""
         first_read = index * R if strong else (index * world + rank) * R
         if dry:
-            _, stats = e.simulate_batch(SEED, first_read, R)
-            return stats
-        _, stats = e.simulate_batch_device(SEED, first_read, R, expected_bytes=int(R * e.expected_record_bytes() * 1.05))
-        return stats
+            out, stats = e.simulate_batch(SEED, first_read, R)
+            return first_read, out, stats
+        out, stats = e.simulate_batch_device(SEED, first_read, R, expected_bytes=int(R * e.expected_record_bytes() * 1.05))
+        return first_read, out, stats
 
     def run_steps(step_indices, indices=None):
         """The device batches of steps `step_indices`, C in flight: worker i owns context i / stream i and takes
@@ -446,7 +517,8 @@ def main():
         (--scaling strong passes its own list of batch indices.)"""
         if indices is None:
             indices = [k * C + b for k in step_indices for b in range(C)]
-        acc = [{'bases': 0, 'passes': 0, 'stages': {}, 'kernels': {}, 'final_launches': 0, 'misses': 0, 'bad': 0, 'host_ms': 0.0, 'error': None, 'lane_useful': 0.0, 'lane_issued': 0.0} for _ in range(C)]
+        acc = [{'bases': 0, 'passes': 0, 'stages': {}, 'kernels': {}, 'final_launches': 0, 'misses': 0, 'bad': 0, 'host_ms': 0.0, 'error': None, 'lane_useful': 0.0, 'lane_issued': 0.0,
+                'last': None} for _ in range(C)]
 
         def worker(i):
             try:
@@ -456,20 +528,23 @@ def main():
                 with ctx:
                     for idx in indices[i::C]:
                         t_call = time.perf_counter()
-                        stats = run_one(engines[i], idx)
+                        acc[i]['last'] = run_one(engines[i], idx)      # (what --dump-outputs writes of the last step)
+                        stats = acc[i]['last'][2]
                         acc[i]['host_ms'] += 1000.0 * (time.perf_counter() - t_call)
                         acc[i]['bases'] += int(stats['seq_len'].sum())
                         acc[i]['bad'] += int((stats['status'] & 0xE).astype(bool).sum())     # RS_TOO_MANY_SEGS | RS_BAND | RS_QMISS
-                        useful, issued = aligner_lane_model(stats)
-                        acc[i]['lane_useful'] += useful; acc[i]['lane_issued'] += issued
+                        if args.full:
+                            useful, issued = aligner_lane_model(stats)
+                            acc[i]['lane_useful'] += useful; acc[i]['lane_issued'] += issued
                         if dry:
                             continue
                         acc[i]['passes'] += engines[i].mutate_passes()
                         for name, ms in engines[i].stage_ms().items():
                             acc[i]['stages'][name] = acc[i]['stages'].get(name, 0.0) + ms
-                        for name, (n_l, ms, b) in engines[i].kernel_stats().items():
-                            k = acc[i]['kernels'].setdefault(name, [0, 0.0, 0.0])
-                            k[0] += n_l; k[1] += ms; k[2] += b
+                        if args.full:
+                            for name, (n_l, ms, b) in engines[i].kernel_stats().items():
+                                k = acc[i]['kernels'].setdefault(name, [0, 0.0, 0.0])
+                                k[0] += n_l; k[1] += ms; k[2] += b
                         acc[i]['final_launches'] += engines[i].final_launches()
                         acc[i]['misses'] += engines[i].window_misses()
                     if not dry:
@@ -543,6 +618,8 @@ def main():
     if strong:
         elapsed = strong_rec['wall_s']             # the clock of the strong line: process start to the last batch of the slowest rank
     value = bases / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [a['last'] for a in acc if a['last'] is not None])
 
     # ---- --d2h: the SAME amount of work through the CLI's own driver (badread_amd.simulate.run_batches: stop rule,
     # pinned ring, writer thread), FASTQ text to /dev/null and through the multi-threaded gzip stage ----
@@ -659,7 +736,30 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
-    # ---- roofline of the kernel that ranks first by summed launch time in THIS run (what rocprofv3 --stats ranks first) ----
+    result['stage_ms_per_device_batch'] = stages
+    result['host_ms_per_device_batch'] = extra['host_ms'] / n_batches        # wall time of one brx_simulate_batch call
+    result['host_cpu'] = {'cpu_seconds_per_device_batch': extra['host_cpu_s'] / n_batches, 'busy_cores_per_rank': extra['host_cpu_s'] / elapsed / world,
+                          'busy_cores_all_ranks': extra['host_cpu_s'] / elapsed, 'usable_cores': usable_cores(),
+                          'note': 'process CPU time of every rank (six batch threads + main each) over the timed region, summed: it must fit the usable cores of the node'}
+    result['scratch_or_output_retries'] = sum(getattr(e, 'retries', 0) for e in engines)
+    result['retry_log'] = [m for e in engines for m in getattr(e, 'retry_log', [])][:8]
+    result['mutate_passes_per_device_batch'] = extra['passes'] / n_batches
+    result['traceback_window_misses_per_step'] = extra['misses'] / args.steps
+    if d2h is not None:
+        for key, leg in (('value_incl_d2h', 'devnull'), ('value_incl_d2h_cold', 'devnull_cold'), ('value_incl_gzip', 'gzip1'), ('value_incl_gzip_device', 'gzip_device')):
+            if leg in d2h:
+                result[key] = d2h[leg]['bases_per_s']
+        result['driver_end_to_end'] = dict(d2h, note='badread_amd.simulate.run_batches (the CLI driver: stop rule, D2H through a ring of pinned '
+                                                      'buffers, writer thread) over the same number of bases, FASTQ to /dev/null and through '
+                                                      '--gzip 1 on all host cores; includes the start-up of its engine clones')
+    if not args.full:
+        result['roofline'] = result['roofline_alu'] = result['cpu_baseline'] = None
+        result['full_note'] = 'per-kernel launch timing, rooflines and the CPU baseline: bench.py --full'
+        print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    # ---- --full: roofline of the kernel that ranks first by summed launch time in THIS run (what rocprofv3 --stats ranks first) ----
     ranked = sorted(((ms, name) for name, (n_l, ms, b) in kern.items() if n_l), reverse=True)
     top = ranked[0][1]
     n_l, ms, kb = kern[top]
@@ -710,22 +810,6 @@ def main():
                                   'lane_note': 'issued instructions are not useful lane-operations: exec_lane_frac = lanes the EXEC mask leaves on (PMC), '
                                                'useful_lane_frac_aligner_model = band words / (64 lanes x words per lane) of the final alignments of THIS run '
                                                '(the kernels that issue more than half of the instructions)'}
-    result['stage_ms_per_device_batch'] = stages
-    result['host_ms_per_device_batch'] = extra['host_ms'] / n_batches        # wall time of one brx_simulate_batch call
-    result['host_cpu'] = {'cpu_seconds_per_device_batch': extra['host_cpu_s'] / n_batches, 'busy_cores_per_rank': extra['host_cpu_s'] / elapsed / world,
-                          'busy_cores_all_ranks': extra['host_cpu_s'] / elapsed, 'usable_cores': usable_cores(),
-                          'note': 'process CPU time of every rank (six batch threads + main each) over the timed region, summed: it must fit the usable cores of the node'}
-    result['scratch_or_output_retries'] = sum(getattr(e, 'retries', 0) for e in engines)
-    result['retry_log'] = [m for e in engines for m in getattr(e, 'retry_log', [])][:8]
-    result['mutate_passes_per_device_batch'] = extra['passes'] / n_batches
-    result['traceback_window_misses_per_step'] = extra['misses'] / args.steps
-    if d2h is not None:
-        for key, leg in (('value_incl_d2h', 'devnull'), ('value_incl_d2h_cold', 'devnull_cold'), ('value_incl_gzip', 'gzip1'), ('value_incl_gzip_device', 'gzip_device')):
-            if leg in d2h:
-                result[key] = d2h[leg]['bases_per_s']
-        result['driver_end_to_end'] = dict(d2h, note='badread_amd.simulate.run_batches (the CLI driver: stop rule, D2H through a ring of pinned '
-                                                      'buffers, writer thread) over the same number of bases, FASTQ to /dev/null and through '
-                                                      '--gzip 1 on all host cores; includes the start-up of its engine clones')
     if world == 1 and args.cpu_seconds > 0:
         result['cpu_baseline'] = cpu_baseline(10_000_000, args.cpu_seconds, args.workload, args.ref_dir)
         result['gpu_over_cpu'] = value / result['cpu_baseline']['value']

@@ -111,3 +111,32 @@ def test_an_oversubscribed_host_is_flagged_in_the_line_not_refused(tmp_path):
     assert line['busy_cores_all_ranks_during_warmup'] > 0.0
     assert line['host_throttled'] == (line['busy_cores_all_ranks_during_warmup'] > 1.25)
     assert line['value'] > 0
+
+
+def test_dump_outputs_same_arguments_same_arrays(tmp_path):
+    """--dump-outputs DIR: after the timed steps the line's run writes what its last step computed as float32 / float64 .npy
+    files under 64 MB; the inputs are seeded, so two runs with the same arguments write the same arrays.  --steps is the number
+    of timed steps, and the dumped reads are those of the last of them."""
+    args = ['--cpu-engine', '--steps', '2', '--warmup', '1', '--reads-per-step', '128', '--streams', '2', '--workload', 'human',
+            '--ref-scale', '0.002', '--gpus', '1']
+    runs = []
+    for name in ('a', 'b'):
+        r = run(args + ['--dump-outputs', str(tmp_path / name)], tmp=tmp_path)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = last_json(r.stdout)
+        assert line['steps'] == 2 and line['warmup'] == 1 and line['ms_per_step'] > 0
+        runs.append(tmp_path / name)
+    import numpy as np
+    names = sorted(os.listdir(runs[0]))
+    assert names == sorted(os.listdir(runs[1]))
+    assert {'read_index.npy', 'stats_seq_len.npy', 'fastq_sample_bytes.npy', 'fastq_batch_byte_sum.npy'} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(runs[0] / n), np.load(runs[1] / n)
+        assert a.dtype in (np.float32, np.float64), n
+        assert a.shape == b.shape and (a == b).all(), n
+        total += os.path.getsize(runs[0] / n)
+    assert total <= 64 << 20
+    index = np.load(runs[0] / 'read_index.npy')
+    assert (index == np.arange(2 * 128, 3 * 128)).all()             # warm-up step 0, timed steps 1 and 2: the reads of step 2
+    assert np.load(runs[0] / 'fastq_sample_bytes.npy').size == np.load(runs[0] / 'fastq_sample_rec_len.npy').sum() > 0

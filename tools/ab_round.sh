@@ -3,8 +3,8 @@
 #   bash tools/ab_round.sh TAG OLD_LIB
 cd ${GRAFT_REPO_ROOT:-/root/repo}; out=gpurun_out; tag=${1:-r03e}; old=${2:-badread_amd/csrc/variants/libbrx_hip_r03.so}
 timeout 110 python -m pytest tests/test_gpu_align.py tests/test_gpu_pipeline.py tests/test_gpu_golden.py -q -x > $out/${tag}_pytest_subset.log 2>&1; echo "subset rc=$?"; tail -2 $out/${tag}_pytest_subset.log
-BRX_LIB_PATH=$PWD/$old timeout 100 python bench.py --steps 3 --cpu-seconds 0 > $out/${tag}_old.json 2> $out/${tag}_old.err
-timeout 150 python bench.py --cpu-seconds 6 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+BRX_LIB_PATH=$PWD/$old timeout 100 python bench.py --full --steps 3 --cpu-seconds 0 > $out/${tag}_old.json 2> $out/${tag}_old.err
+timeout 150 python bench.py --full --cpu-seconds 6 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 for f in old bench; do python -c "
 import json
 d=json.loads([l for l in open('$out/${tag}_$f.json') if l.startswith('{')][-1])

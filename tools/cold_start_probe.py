@@ -1,7 +1,7 @@
 """Where does the first batch of a process spend its time?  (tools/; run on the GPU box)"""
 import io, sys, time, os
 sys.path.insert(0, os.getcwd())
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '40')
+os.environ.setdefault('GPU_MAX_HW_QUEUES', '32')
 import torch, bench
 from badread_amd.engine import HipEngine
 wl = bench.build_workload(io.StringIO(), 'human', bench.default_ref_dir())

@@ -19,9 +19,9 @@ cp profiles/pmc_traffic.json $out/${tag}_pmc_traffic.json          # profiles/ o
 ( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$root/$out/${tag}_tl" -o t -- \
     python "$root/bench.py" --steps 1 --warmup 1 --streams 1 --reads-per-step 65536 --cpu-seconds 0 > /dev/null 2> "$root/$out/${tag}_tl.err" )
 python tools/batch_timeline.py $out/${tag}_tl/*kernel_trace.csv > $out/${tag}_batch_timeline.json 2>> $out/${tag}_tl.err; rm -rf $out/${tag}_tl
-timeout 400 python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
-timeout 300 python bench.py --workload hifi --cpu-seconds 8 > $out/${tag}_bench_hifi.json 2> $out/${tag}_bench_hifi.err
-timeout 300 python bench.py --workload kpn --cpu-seconds 6 > $out/${tag}_bench_kpn.json 2> $out/${tag}_bench_kpn.err
+timeout 400 python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout 300 python bench.py --full --workload hifi --cpu-seconds 8 > $out/${tag}_bench_hifi.json 2> $out/${tag}_bench_hifi.err
+timeout 300 python bench.py --full --workload kpn --cpu-seconds 6 > $out/${tag}_bench_kpn.json 2> $out/${tag}_bench_kpn.err
 for f in bench bench_hifi bench_kpn; do python -c "
 import json
 d=json.loads([l for l in open('$out/${tag}_$f.json') if l.startswith('{')][-1])

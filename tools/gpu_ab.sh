@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 for spec in "$@"; do
   envs="${spec%%|*}"; args="${spec#*|}"
-  env $envs timeout 200 python bench.py --cpu-seconds 0 $args 2>/tmp/err.txt | python -c "
+  env $envs timeout 200 python bench.py --full --cpu-seconds 0 $args 2>/tmp/err.txt | python -c "
 import json, sys
 try:
     d = json.loads(sys.stdin.read()); s = d['stage_ms_per_device_batch']; k = d['kernels_per_device_batch']

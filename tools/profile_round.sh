@@ -11,7 +11,7 @@ root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d "$out/${tag}_trace" -o t -- python "$root/bench.py" --workload $wl --steps 4 --warmup 1 --cpu-seconds 0 > "$out/${tag}_bench_profiled.json" 2> "$out/${tag}_trace.err"
+timeout 600 rocprofv3 --kernel-trace --stats -d "$out/${tag}_trace" -o t -- python "$root/bench.py" --full --workload $wl --steps 4 --warmup 1 --cpu-seconds 0 > "$out/${tag}_bench_profiled.json" 2> "$out/${tag}_trace.err"
 python "$root/tools/export_prof.py" "$(ls "$out/${tag}_trace"/*.db | head -1)" "$out/${tag}_bench_kernel_stats.csv" >> "$out/${tag}_trace.err" 2>&1
 i=0
 for ctrs in "${@:3}"; do
