@@ -84,6 +84,10 @@ SIMULATE_OPTIONS = [
                                       '--gzip-device the compressed bytes; with --gzip the compressed bytes per batch go to '
                                       'PREFIX.<rank>.zparts beside them), instead of all records travelling to rank 0 and through one '
                                       'stdout; the same reads, the same stopping point')),
+        ('--truth-paf', dict(type=str, default=None, dest='truth_paf', metavar='PATH',
+                             help='Also write the true alignment of every read against the reference to PATH as PAF (plain text): '
+                                  'one record per stretch of the read that comes consecutively from one contig and strand, with a '
+                                  'cg:Z: CIGAR; with --output-shards every rank writes PATH.<rank>')),
         ('--gpu-streams', dict(type=int, default=None, dest='gpu_streams',
                                help='Device batches in flight per GPU, each on its own HIP stream (default: 6)')),
     ]),
@@ -161,6 +165,9 @@ def check_simulate_args(args):
     """Validate and derive the fields simulate() reads (mean_frag_length, identity triple, glitch_*)."""
     if not pathlib.Path(args.reference).is_file():
         sys.exit(f'Error: {args.reference} is not a file')
+    truth_paf = getattr(args, 'truth_paf', None)
+    if truth_paf is not None and not pathlib.Path(truth_paf).resolve().parent.is_dir():
+        sys.exit(f'Error: the directory of --truth-paf {truth_paf} does not exist')
     for value, names, flag in ((args.error_model, ERROR_MODEL_NAMES, '--error_model'),
                                (args.qscore_model, QSCORE_MODEL_NAMES, '--qscore_model')):
         if value.lower() not in names and not pathlib.Path(value).is_file():

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "brx_kernels.h"
+#include "brx_paf.h"
 
 #define BRX_KEV_MAX 2048
 
@@ -73,6 +74,11 @@ struct brx_ctx {
     int kev_n, kev_dropped;
     brx_kernel_stat kstat[BRX_KERN_COUNT];
     int profile;                 /* BRX_PROFILE=1: the mutate kernels time their phases (brx_last_phase_cycles) */
+    /* brx_emit_paf: what the last brx_simulate_batch left in the arena (valid until the next call that reuses the arena) */
+    bool paf_valid;
+    BrxDev paf_dev;
+    const RS *paf_rs; const PSeg *paf_segs; uint32_t paf_reads;
+    uint8_t *h_paf, *d_paf; size_t paf_bytes;      /* pinned (mapped): per-read PAF bytes, primary records and offsets */
     char err[512];
 };
 
@@ -146,6 +152,7 @@ static void release(brx_ctx *c) {
     if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
     if (c->h_totals) (void)hipHostFree(c->h_totals);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
+    if (c->h_paf) (void)hipHostFree(c->h_paf);
     free(c);
 }
 
@@ -228,28 +235,28 @@ extern "C" const char *brx_last_error(const brx_ctx *c) { return c ? c->err : g_
 extern "C" int brx_set_reference(brx_ctx *c, const brx_reference *r) {
     if (!c || !r) return BRX_E_ARG;
     if (r->n_contigs == 0 || !r->d_packed || !r->d_contigs) return fail(c, BRX_E_ARG, "reference has no contigs");
-    c->dev.ref = *r; c->has_ref = true; return BRX_OK;
+    c->dev.ref = *r; c->has_ref = true; c->paf_valid = false; return BRX_OK;
 }
 extern "C" int brx_set_error_model(brx_ctx *c, const brx_error_model *m) {
     if (!c || !m) return BRX_E_ARG;
     if (m->k < 1 || m->k > 16) return fail(c, BRX_E_ARG, "error model k-mer size %d out of range", m->k);
     if (m->type != 0 && (!m->d_rowx || !m->d_altx))
         return fail(c, BRX_E_ARG, "error model without its lookup-order tables (d_rowx, d_altx: include/brx.h)");
-    c->dev.em = *m; c->has_em = true; return BRX_OK;
+    c->dev.em = *m; c->has_em = true; c->paf_valid = false; return BRX_OK;
 }
 extern "C" int brx_set_qscore_model(brx_ctx *c, const brx_qscore_model *m) {
     if (!c || !m) return BRX_E_ARG;
     if (m->k < 1 || (m->k & 1) == 0 || 2 * m->k + m->gap_bits * (m->k - 1) > 56 || (m->hash_size & (m->hash_size - 1)))
         return fail(c, BRX_E_ARG, "unsupported qscore model geometry");
-    c->dev.qm = *m; c->has_qm = true; return BRX_OK;
+    c->dev.qm = *m; c->has_qm = true; c->paf_valid = false; return BRX_OK;
 }
 extern "C" int brx_set_params(brx_ctx *c, const brx_sim_params *p) {
     if (!c || !p) return BRX_E_ARG;
-    c->dev.p = *p; c->has_params = true; return BRX_OK;
+    c->dev.p = *p; c->has_params = true; c->paf_valid = false; return BRX_OK;
 }
 extern "C" int brx_set_scratch(brx_ctx *c, void *d_scratch, size_t bytes) {
     if (!c) return BRX_E_ARG;
-    c->scratch = (uint8_t *)d_scratch; c->scratch_bytes = bytes; return BRX_OK;
+    c->scratch = (uint8_t *)d_scratch; c->scratch_bytes = bytes; c->paf_valid = false; return BRX_OK;
 }
 extern "C" size_t brx_scratch_needed(const brx_ctx *c) { return c ? c->scratch_needed : 0; }
 extern "C" size_t brx_output_needed(const brx_ctx *c) { return c ? c->output_needed : 0; }
@@ -406,6 +413,7 @@ static int run_pipeline_impl(brx_ctx *c, uint64_t seed, uint64_t first_read, uin
 static int run_pipeline(brx_ctx *c, uint64_t seed, uint64_t first_read, uint32_t n_reads, bool raw,
                         const uint8_t *d_frags, const uint64_t *d_frag_off, const double *d_target,
                         uint8_t *d_out, size_t out_cap, brx_read_stats *d_stats, size_t *out_bytes, hipStream_t st) {
+    if (c) c->paf_valid = false;
     const int rc = run_pipeline_impl(c, seed, first_read, n_reads, raw, d_frags, d_frag_off, d_target, d_out, out_cap, d_stats, out_bytes, st);
     if (rc != BRX_OK && rc != BRX_E_ARG && rc != BRX_E_STATE) {
         (void)hipStreamSynchronize(st);
@@ -1225,6 +1233,7 @@ static int run_pipeline_impl(brx_ctx *c, uint64_t seed, uint64_t first_read, uin
         if (c->kstat[BRX_KERN_FIN_QSCORE].launches) c->stage_ms[BRX_STAGE_QSCORE] = c->kstat[BRX_KERN_FIN_QSCORE].ms / (float)c->kstat[BRX_KERN_FIN_QSCORE].launches;
     }
     if (out_bytes) *out_bytes = (size_t)rec_bytes;
+    if (!raw) { c->paf_dev = dev; c->paf_rs = rs; c->paf_segs = segs; c->paf_reads = n_reads; c->paf_valid = true; }
     /* a read that exhausted its 1000 tries is fatal in the reference (simulate.py:164) */
     if (!raw) {
         { int rc_ = fetch_rs(st); if (rc_) return rc_; }
@@ -1259,6 +1268,7 @@ extern "C" int brx_align_batch(brx_ctx *c, uint32_t n_pairs, const uint8_t *d_qu
                                int32_t *d_dist, uint32_t *d_ncols, uint32_t *d_nmatch, uint8_t *d_ops,
                                const uint64_t *d_ops_off, void *hip_stream) {
     if (!c || !d_q_off || !d_t_off || !d_k_hint || !d_dist || !d_ncols || !d_nmatch) return BRX_E_ARG;
+    c->paf_valid = false;
     if (!c->scratch) return fail(c, BRX_E_STATE, "scratch arena not set");
     if (n_pairs == 0) return BRX_OK;
     hipStream_t st = (hipStream_t)hip_stream;
@@ -1333,6 +1343,7 @@ extern "C" int brx_align_batch(brx_ctx *c, uint32_t n_pairs, const uint8_t *d_qu
 static_assert(sizeof(brx_model_job) == sizeof(BrxMbJob), "brx_model_job and BrxMbJob must have the same layout");
 extern "C" int brx_model_count(brx_ctx *c, int kind, const brx_model_job *job, void *hip_stream) {
     if (!c || !job || (kind != 0 && kind != 1)) return BRX_E_ARG;
+    c->paf_valid = false;
     if (job->n_align == 0 || job->n_cols == 0) return BRX_OK;
     if (kind == 0 && (job->k < 2 || 2 * job->k + 5 + 2 * BRX_MB_MAX_READ_KMER > 64)) return fail(c, BRX_E_ARG, "error model k-mer size %u not supported (2..8)", job->k);
     if (kind == 1 && (job->n_ksizes < 1 || job->n_ksizes > 16 || job->max_del > 15)) return fail(c, BRX_E_ARG, "qscore model: k_size up to 31, max_del up to 15");
@@ -1395,6 +1406,43 @@ extern "C" int brx_gzip_device(brx_ctx *c, const void *d_in, size_t n_bytes, con
     HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)((total + 7) & ~(uint64_t)3), st));
     hipLaunchKernelGGL(k_gz_pack, dim3(grid), dim3(64), 0, st, (const uint8_t *)d_in, (uint64_t)n_bytes, d_block_off, nb, (uint8_t *)d_out, member_off, tabs, offs, crcs);
     { int rcw = wait_stream(c, st, "brx_gzip_device (pack)"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    *out_bytes = (size_t)total;
+    return BRX_OK;
+}
+
+/* ---- truth alignments of the last simulate batch (brx_paf.h) ---- */
+extern "C" int brx_emit_paf(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+    if (!c || !out_bytes) return BRX_E_ARG;
+    *out_bytes = 0;
+    if (!c->paf_valid) return fail(c, BRX_E_STATE, "no simulate batch on this context to emit truth alignments for");
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint32_t n = c->paf_reads;
+    const size_t len_at = 0, best_at = ((size_t)n * 4 + 255) & ~(size_t)255, off_at = best_at + (((size_t)n * 4 + 255) & ~(size_t)255);
+    const size_t need = off_at + ((size_t)n + 1) * 8;
+    if (c->paf_bytes < need) {
+        if (c->h_paf) { (void)hipHostFree(c->h_paf); c->h_paf = c->d_paf = nullptr; c->paf_bytes = 0; }
+        HIPCHK(c, hipHostMalloc((void **)&c->h_paf, need, hipHostMallocMapped));
+        void *dp = nullptr;
+        HIPCHK(c, hipHostGetDevicePointer(&dp, c->h_paf, 0));
+        c->d_paf = (uint8_t *)dp; c->paf_bytes = need;
+    }
+    uint32_t *len = (uint32_t *)(c->d_paf + len_at), *best = (uint32_t *)(c->d_paf + best_at);
+    uint64_t *off = (uint64_t *)(c->d_paf + off_at);
+    if (n) hipLaunchKernelGGL(k_paf_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, (const uint8_t *)c->scratch, len, best);
+    hipLaunchKernelGGL(k_paf_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
+    { int rcw = wait_stream(c, st, "k_paf_size"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    const uint64_t total = ((const uint64_t *)(c->h_paf + off_at))[n];
+    if (total > out_cap || (total && !d_out)) {
+        c->output_needed = total;
+        return fail(c, BRX_E_OUTPUT, "truth alignment buffer too small: need %llu bytes", (unsigned long long)total);
+    }
+    if (n && total) hipLaunchKernelGGL(k_paf_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, (const uint8_t *)c->scratch,
+                                       (const uint64_t *)off, (const uint32_t *)best, d_out);
+    if (d_read_off) HIPCHK(c, hipMemcpyAsync(d_read_off, c->h_paf + off_at, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
+    { int rcw = wait_stream(c, st, "k_paf_write"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
     *out_bytes = (size_t)total;
     return BRX_OK;

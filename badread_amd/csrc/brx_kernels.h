@@ -1384,13 +1384,18 @@ __device__ inline uint64_t milli_round(double v) {
     if (rem > half || (rem == half && (q & 1ull))) q += 1;
     return q;
 }
+/* the read's name, uuid.UUID(int=getrandbits(128)): the FASTQ header and the PAF records (brx_paf.h) */
+template <class S>
+__device__ void put_uuid(S &s, const BrxDev &d, uint64_t read) {
+    uint32_t w[4];
+    brx_draw4(d.seed, read, BRX_ST_NAME, 0, w);
+    put_hex(s, w[0], 8); s.put('-'); put_hex(s, w[1] >> 16, 4); s.put('-'); put_hex(s, w[1] & 0xFFFFu, 4); s.put('-');
+    put_hex(s, w[2] >> 16, 4); s.put('-'); put_hex(s, w[2] & 0xFFFFu, 4); put_hex(s, w[3], 8);
+}
 template <class S>
 __device__ void put_header(S &s, const BrxDev &d, uint64_t read, const RS &r, const PPiece *pieces) {
-    uint32_t w[4];
-    brx_draw4(d.seed, read, BRX_ST_NAME, 0, w);            /* uuid.UUID(int=getrandbits(128)) */
     s.put('@');
-    put_hex(s, w[0], 8); s.put('-'); put_hex(s, w[1] >> 16, 4); s.put('-'); put_hex(s, w[1] & 0xFFFFu, 4); s.put('-');
-    put_hex(s, w[2] >> 16, 4); s.put('-'); put_hex(s, w[2] & 0xFFFFu, 4); put_hex(s, w[3], 8); s.put(' ');
+    put_uuid(s, d, read); s.put(' ');
     for (uint32_t i = 0; i < r.n_pieces; ++i) {
         const PPiece pc = pieces[r.piece_off + i];
         uint32_t type = pc.w0 & 3u, strand = (pc.w0 >> 2) & 1u, contig = pc.w0 >> 3;

@@ -1,0 +1,253 @@
+/*
+ * brx_paf.h -- truth alignments of a simulate batch as PAF text (brx_emit_paf).  Included once by brx_hip.hip after
+ * brx_kernels.h.
+ *
+ * A read's truth is the composition of two things the batch leaves in the arena: the provenance of every fragment base
+ * (the PSeg list of k_plan_fill) and the final alignment of the errored read (query) against the padded fragment
+ * (target), one op byte per column (0 '=' 1 'X' 2 'I' 3 'D', the last RS.n_cols bytes before ops_off + n + m).
+ *
+ * A record is a maximal run of columns whose target bases (=, X, D) all come from the reference, consecutively on one
+ * contig and strand, and whose query bases (=, X, I) are all kept in the FASTQ read; it is trimmed to its first and last
+ * =/X column.  Over the M columns (= and X) of good provenance this means: two consecutive ones belong to one record
+ * unless a column between them (the later one included) does not continue the run -- a "break".
+ *
+ * One wave per read, 64 columns per step:
+ *   paf_read   walks every column once: r / f from ballot prefix counts, origin from the segment list (a scalar cursor that
+ *              only moves forward), break flags against the neighbour column; a record is closed when the next one starts
+ *   paf_record sizes a record (a sweep over its columns: op counts and the text length of its CIGAR) and, for the writing
+ *              sink, writes it (a second sweep: every lane that ends a CIGAR run places its text with a wave prefix sum;
+ *              '-' records mirror the runs, the convention of minimap2 that alignment.py undoes)
+ * The same code sizes (PafCount) and writes (PafWrite): k_paf_size / k_paf_scan / k_paf_write, the pattern of
+ * k_recsize / k_scan_rec / k_emit.
+ */
+#ifndef BRX_PAF_H
+#define BRX_PAF_H
+
+#define BRX_PAF_NOKEY (~0ull)          /* no origin: pads, adapters, junk, random sequence, glitch inserts */
+
+struct PafCount { static constexpr bool write = false; uint8_t *out; };
+struct PafWrite { static constexpr bool write = true; uint8_t *out; };
+
+__device__ __forceinline__ uint32_t paf_digits(uint32_t v) { uint32_t n = 1; while (v >= 10) { v /= 10; ++n; } return n; }
+__device__ __forceinline__ int paf_top(uint64_t bits) { return 63 - __builtin_clzll(bits); }     /* bits != 0 */
+__device__ __forceinline__ uint32_t paf_cls(uint32_t op) { return op <= 1 ? 0u : op; }              /* M (= or X), I, D */
+
+struct PafRec { uint32_t c0, c1, r0; uint64_t key0; };          /* first / last M column, read index and origin of the first */
+struct PafRead {                                                 /* what a record needs of its read (uniform over the wave) */
+    const uint8_t *ops; uint64_t read; uint32_t seq_len, start_trim;
+    uint32_t best;                   /* the primary record (writing sink: found by the sizing pass) */
+    uint32_t n_rec, top, top_set; int64_t top_as; uint64_t at;      /* records so far, the first of the highest AS among them */
+};
+
+/* The header fields of a record (qname .. cg:Z:) and its tail (\tNM:i:..\tAS:i:..\n). */
+template <class B>
+__device__ void paf_head(B &b, const BrxDev &d, const PafRead &R, const PafRec &q, uint32_t qlen_cols, uint32_t tspan, uint32_t n_eq,
+                         uint32_t cols, bool primary) {
+    const uint32_t cs = (uint32_t)(q.key0 >> 32), contig = cs >> 1, strand = cs & 1u, p0 = (uint32_t)q.key0;
+    const brx_contig ct = d.ref.d_contigs[contig];
+    put_uuid(b, d, R.read); b.put('\t');
+    put_dec(b, R.seq_len); b.put('\t');
+    put_dec(b, q.r0 - R.start_trim); b.put('\t'); put_dec(b, q.r0 - R.start_trim + qlen_cols); b.put('\t');
+    b.put(strand ? '-' : '+'); b.put('\t');
+    for (uint32_t x = 0; x < ct.name_len; ++x) b.put(d.ref.d_names[ct.name_off + x]);
+    b.put('\t'); put_dec(b, ct.length); b.put('\t');
+    const uint64_t ts = strand ? (uint64_t)ct.length - (uint64_t)p0 - tspan : (uint64_t)p0;
+    put_dec(b, ts); b.put('\t'); put_dec(b, ts + tspan); b.put('\t');
+    put_dec(b, n_eq); b.put('\t'); put_dec(b, cols); put_str(b, "\t60\ttp:A:"); b.put(primary ? 'P' : 'S'); put_str(b, "\tcg:Z:");
+}
+template <class B>
+__device__ void paf_tail(B &b, uint32_t nm, int64_t as) {
+    put_str(b, "\tNM:i:"); put_dec(b, nm); put_str(b, "\tAS:i:");
+    if (as < 0) { b.put('-'); put_dec(b, (uint64_t)(-as)); } else put_dec(b, (uint64_t)as);
+    b.put('\n');
+}
+
+/* One record [q.c0, q.c1] of the read: sized, and written when S writes.  Every lane calls it (wave-uniform arguments). */
+template <class S>
+__device__ void paf_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q) {
+    const int lane = lane_id();
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint32_t cnt[4] = {0, 0, 0, 0};
+    uint32_t text = 0, run_start = q.c0;
+    /* sweep 1: op counts and the CIGAR's text length.  A lane whose column ends a run (the next column is another class, or
+       the record ends) owns that run's text: its decimal length and the letter. */
+    for (uint32_t b = q.c0; b <= q.c1; b += 64) {
+        const uint32_t c = b + lane;
+        const bool in = c <= q.c1;
+        const uint32_t op = in ? R.ops[c] : 0u;
+        const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
+        const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
+        const bool rs = in && (c == q.c0 || paf_cls(prev) != paf_cls(op));
+        const bool re = in && (c == q.c1 || paf_cls(next) != paf_cls(op));
+        const uint64_t rmask = __ballot(rs);
+        const uint64_t mine = rmask & (below | (1ull << lane));
+        const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
+        const uint32_t t = re ? paf_digits(c - s0 + 1) + 1u : 0u;
+        text += wave_sum(t);
+        for (uint32_t o = 0; o < 4; ++o) cnt[o] += (uint32_t)__popcll(__ballot(in && op == o));
+        if (rmask) run_start = b + (uint32_t)paf_top(rmask);
+    }
+    const uint32_t cols = q.c1 - q.c0 + 1u;
+    const uint32_t nm = cnt[1] + cnt[2] + cnt[3];
+    const int64_t as = (int64_t)cnt[0] - (int64_t)nm;
+    const uint32_t qcols = cnt[0] + cnt[1] + cnt[2], tspan = cnt[0] + cnt[1] + cnt[3];
+    const bool primary = S::write && R.n_rec == R.best;
+    if (!R.top_set || as > R.top_as) { R.top_as = as; R.top = R.n_rec; R.top_set = 1; }   /* the first of equals */
+    R.n_rec += 1;
+    CountSink hc; hc.n = 0;
+    paf_head(hc, d, R, q, qcols, tspan, cnt[0], cols, primary);
+    CountSink tc; tc.n = 0;
+    paf_tail(tc, nm, as);
+    if (S::write) {
+        uint8_t *o = sink.out + R.at;
+        if (lane == 0) {
+            ByteSink h; h.p = o; h.n = 0;
+            paf_head(h, d, R, q, qcols, tspan, cnt[0], cols, primary);
+            ByteSink tl; tl.p = o + hc.n + text; tl.n = 0;
+            paf_tail(tl, nm, as);
+        }
+        uint8_t *cig = o + hc.n;
+        const bool minus = (q.key0 >> 32) & 1u;
+        /* sweep 2: every run's text at its place; the prefix sum of the text lengths over the lanes gives it */
+        uint32_t done = 0;
+        run_start = q.c0;
+        for (uint32_t b = q.c0; b <= q.c1; b += 64) {
+            const uint32_t c = b + lane;
+            const bool in = c <= q.c1;
+            const uint32_t op = in ? R.ops[c] : 0u;
+            const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
+            const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
+            const bool rs = in && (c == q.c0 || paf_cls(prev) != paf_cls(op));
+            const bool re = in && (c == q.c1 || paf_cls(next) != paf_cls(op));
+            const uint64_t rmask = __ballot(rs);
+            const uint64_t mine = rmask & (below | (1ull << lane));
+            const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
+            const uint32_t len = c - s0 + 1u;
+            const uint32_t t = re ? paf_digits(len) + 1u : 0u;
+            const uint32_t incl = wave_incl_scan(t);
+            if (re) {
+                const uint32_t fwd = done + incl - t;
+                uint8_t *p = cig + (minus ? text - fwd - t : fwd);
+                uint32_t v = len;
+                for (uint32_t x = t - 1; x-- > 0;) { p[x] = (uint8_t)('0' + v % 10); v /= 10; }
+                const uint32_t cl = paf_cls(op);
+                p[t - 1] = (uint8_t)(cl == 0 ? 'M' : cl == 2 ? 'I' : 'D');
+            }
+            done += wave_bcast_u32(incl, 63);
+            if (rmask) run_start = b + (uint32_t)paf_top(rmask);
+        }
+    }
+    R.at += hc.n + text + tc.n;
+}
+
+/* Every record of read r, in column order (= increasing qstart); R.at advances by the read's PAF bytes, R.top = its primary. */
+template <class S>
+__device__ void paf_read(S &sink, const BrxDev &d, const RS &s, uint32_t r, const PSeg *segs, const uint8_t *arena, PafRead &R) {
+    const int lane = lane_id();
+    const uint64_t below = (1ull << lane) - 1ull;
+    const uint32_t n = s.n, m = s.m, ncols = s.n_cols, k = (uint32_t)d.em.k, flen = s.frag_len;
+    const uint32_t lo = s.start_trim, hi = (s.end_trim == 0 || m < s.end_trim) ? 0u : m - s.end_trim;      /* kept: lo <= r < hi */
+    R.ops = arena + s.ops_off + (uint64_t)n + (uint64_t)m - ncols;
+    R.read = d.first_read + r; R.seq_len = s.seq_len; R.start_trim = lo;
+    R.n_rec = 0; R.top = 0; R.top_set = 0; R.top_as = 0;
+    const PSeg *sg = segs + s.seg_off;
+    uint32_t r_base = 0, f_base = 0, cur = 0;
+    uint64_t carry_key = BRX_PAF_NOKEY, last_m = 0;
+    bool carry_good = false, pend = true, open = false;
+    PafRec q; q.c0 = q.c1 = q.r0 = 0; q.key0 = 0;
+    for (uint32_t b = 0; b < ncols; b += 64) {
+        const uint32_t c = b + lane;
+        const bool in = c < ncols;
+        const uint32_t op = in ? R.ops[c] : 0u;
+        const bool isq = in && op != 3u, ist = in && op != 2u;
+        const uint64_t qm = __ballot(isq), tm = __ballot(ist);
+        const uint32_t rr = r_base + (uint32_t)__popcll(qm & below), ff = f_base + (uint32_t)__popcll(tm & below);
+        /* origin of the target base: the segment cursor moves forward while some lane lies beyond the current segment */
+        const uint32_t fq = ff - k;
+        bool need = ist && ff >= k && fq < flen;
+        uint64_t key = BRX_PAF_NOKEY;
+        while (__ballot(need) && cur < s.n_segs) {        /* the segments cover [0, frag_len): the bound only guards the load */
+            const PSeg g = sg[cur];
+            if (need && fq < g.dst + g.len) {
+                if ((g.w0 & 3u) == SEG_REF)
+                    key = ((uint64_t)((g.w0 >> 5) * 2u + ((g.w0 >> 2) & 7u)) << 32) | (uint64_t)(g.start + (fq - g.dst));
+                need = false;
+            }
+            if (__ballot(need)) ++cur;
+        }
+        if (cur >= s.n_segs) cur = s.n_segs ? s.n_segs - 1u : 0u;
+        const bool kept = rr >= lo && rr < hi;
+        const bool good = in && (!ist || key != BRX_PAF_NOKEY) && (!isq || kept);
+        /* the previous column's state and the previous target column's origin */
+        const bool up_good = __shfl_up((int)good, 1, 64) != 0;
+        const bool prev_good = lane == 0 ? carry_good : up_good;
+        const uint64_t tb = tm & below;
+        const uint64_t up_key = wave_bcast_u64(key, tb ? paf_top(tb) : lane);
+        const uint64_t prev_key = tb ? up_key : carry_key;
+        const bool link = good && prev_good && (!ist || (prev_key != BRX_PAF_NOKEY && prev_key + 1 == key));
+        const bool gm = good && op <= 1u;
+        const uint64_t mm = __ballot(gm), bm = __ballot(in && !link);
+        /* an M column starts a record when a break lies after the previous M column, up to itself */
+        const uint64_t pmb = mm & below, lbb = bm & (below | (1ull << lane));
+        const int pm = pmb ? paf_top(pmb) : -1, lb = lbb ? paf_top(lbb) : -1;
+        const bool start = gm && (lb > pm || (pm < 0 && lb < 0 && pend));
+        uint64_t sm = __ballot(start);
+        while (sm) {
+            const int L = __builtin_ctzll(sm);
+            sm &= sm - 1ull;
+            const uint64_t before = mm & ((1ull << L) - 1ull);
+            const uint32_t r0 = wave_bcast_u32(rr, L);
+            const uint64_t k0 = wave_bcast_u64(key, L);
+            if (open) { q.c1 = before ? b + (uint32_t)paf_top(before) : (uint32_t)last_m; paf_record(sink, d, R, q); }
+            q.c0 = b + (uint32_t)L; q.r0 = r0; q.key0 = k0; open = true;
+        }
+        if (mm) {
+            const int hm = paf_top(mm);
+            last_m = b + (uint32_t)hm;
+            pend = (bm & ~((2ull << hm) - 1ull)) != 0;
+        } else pend = pend || bm != 0;
+        carry_good = wave_bcast_u32((uint32_t)good, 63) != 0;
+        if (tm) carry_key = wave_bcast_u64(key, paf_top(tm));
+        r_base += (uint32_t)__popcll(qm); f_base += (uint32_t)__popcll(tm);
+    }
+    if (open) { q.c1 = (uint32_t)last_m; paf_record(sink, d, R, q); }
+}
+
+__device__ __forceinline__ bool paf_has_records(const RS &s) {
+    return s.rec_len != 0 && s.n_cols != 0 && !(s.status & (BRX_RS_BAND | BRX_RS_NOFRAG | BRX_RS_EMPTY | BRX_RS_TOO_MANY_SEGS));
+}
+
+/* bytes and primary record of every read */
+__global__ void __launch_bounds__(64) k_paf_size(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t *len, uint32_t *best) {
+    const uint32_t r = blockIdx.x;
+    const RS s = rs[r];
+    PafRead R; R.at = 0; R.best = 0; R.top = 0;
+    if (paf_has_records(s)) { PafCount k_; k_.out = nullptr; paf_read(k_, d, s, r, segs, arena, R); }
+    if (lane_id() == 0) { len[r] = (uint32_t)R.at; best[r] = R.top; }
+}
+
+/* read offsets: off[r] (n_reads + 1 entries, the last = total bytes), and the caller's copy when it asks for one */
+__global__ void __launch_bounds__(64) k_paf_scan(uint32_t n_reads, const uint32_t *len, uint64_t *off) {
+    const int lane = lane_id();
+    uint64_t run = 0;
+    for (uint32_t base = 0; base < n_reads; base += 64) {
+        const uint32_t r = base + lane;
+        const uint32_t l = r < n_reads ? len[r] : 0u;
+        const uint32_t inc = wave_incl_scan(l);         /* a 64-read group stays far below 2^32 bytes */
+        if (r < n_reads) off[r] = run + inc - l;
+        run += wave_bcast_u32(inc, 63);
+    }
+    if (lane == 0) off[n_reads] = run;
+}
+
+__global__ void __launch_bounds__(64) k_paf_write(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, const uint64_t *off,
+                                                   const uint32_t *best, uint8_t *out) {
+    const uint32_t r = blockIdx.x;
+    const RS s = rs[r];
+    if (!paf_has_records(s)) return;
+    PafRead R; R.at = off[r]; R.best = best[r];
+    PafWrite w; w.out = out;
+    paf_read(w, d, s, r, segs, arena, R);
+}
+
+#endif /* BRX_PAF_H */

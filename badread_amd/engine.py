@@ -78,6 +78,8 @@ READ_STATS_DTYPE = np.dtype([('status', '<u4'), ('frag_len', '<u4'), ('seq_len',
 assert READ_STATS_DTYPE.itemsize == 64
 
 RS_NOFRAG, RS_TOO_MANY_SEGS, RS_BAND, RS_QMISS, RS_EMPTY = 1, 2, 4, 8, 16
+# --truth-paf: PAF bytes per FASTQ byte that a batch's buffer is first sized for (measured 0.079 on configs[3]: profiles/truth_paf.md)
+PAF_SHARE = 0.1
 E_SCRATCH, E_OUTPUT, E_NOFRAG = -3, -4, -5
 STAGE_NAMES = ('plan', 'build', 'mutate', 'scan', 'final', 'emit', 'align1', 'qscore')
 # kernel classes of brx_last_kernel_stats (include/brx.h: BRX_KERN_*), with the names a rocprofv3 kernel trace shows
@@ -287,6 +289,9 @@ def bind_library(lib):
                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
     lib.brx_model_count.restype = ctypes.c_int
     lib.brx_model_count.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(BrxModelJob), ctypes.c_void_p]
+    lib.brx_emit_paf.restype = ctypes.c_int
+    lib.brx_emit_paf.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t),
+                                 ctypes.c_void_p]
     lib.brx_last_mutate_passes.restype = ctypes.c_uint32
     lib.brx_last_mutate_passes.argtypes = [ctypes.c_void_p]
     lib.brx_last_final_launches.restype = ctypes.c_uint32
@@ -526,6 +531,24 @@ class HipEngine(EngineBase):
             self.ctx, seed, first_read, n_reads, o, cap, st, ob, self._stream()), n_reads, guess, allow_nofrag)
         stats = self._stats[:n_reads * READ_STATS_DTYPE.itemsize].cpu().numpy().view(READ_STATS_DTYPE)
         return self._out[:nbytes], stats
+
+    def emit_paf_device(self, n_reads):
+        """Truth alignments (PAF text, include/brx.h brx_emit_paf) of the last simulate_batch(_device) of this engine, which had
+        `n_reads` reads: (device uint8 tensor of the records in read order, numpy uint64 offsets of each read's records, n_reads + 1
+        entries).  The tensor is a fresh one: the engine may take its next batch at once."""
+        torch = self.torch
+        off = torch.zeros(n_reads + 1, dtype=torch.int64, device=self.device)
+        cap = int(n_reads * PAF_SHARE * self.expected_record_bytes()) + (1 << 16)
+        for _ in range(2):
+            out = torch.empty(cap, dtype=torch.uint8, device=self.device)
+            got = ctypes.c_size_t(0)
+            rc = self.lib.brx_emit_paf(self.ctx, ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(off.data_ptr()),
+                                       ctypes.byref(got), self._stream())
+            if rc != E_OUTPUT:
+                break
+            cap = int(self.lib.brx_output_needed(self.ctx)) + 64
+        self._check(rc)
+        return out[:got.value], off.cpu().numpy().view(np.uint64)
 
     def simulate_batch(self, seed, first_read, n_reads, allow_nofrag=False):
         out, stats = self.simulate_batch_device(seed, first_read, n_reads, allow_nofrag=allow_nofrag)

@@ -27,7 +27,7 @@ import time
 import numpy as np
 
 from . import settings
-from .engine import RS_BAND, RS_NOFRAG, RS_QMISS, RS_TOO_MANY_SEGS, SimParams
+from .engine import PAF_SHARE, RS_BAND, RS_NOFRAG, RS_QMISS, RS_TOO_MANY_SEGS, SimParams
 from .error_model import ErrorModel
 from .fragment_lengths import FragmentLengths
 from .identities import Identities
@@ -466,7 +466,7 @@ class _ArenaPrefetch(object):
             pass
 
     @staticmethod
-    def for_job(engine, target_size, mean_length, error_rate, in_flight, world):
+    def for_job(engine, target_size, mean_length, error_rate, in_flight, world, truth_paf=False):
         """Arenas for the batches in flight of THIS job on THIS device, or None (not a GPU engine, a job of one small batch,
         BRX_ARENA_PREFETCH=0).  How many: what the job will use and the free memory holds (_BatchPool.engines_that_fit's rule)."""
         # Measured (profiles/r05i_arena_prefetch.json, r05k_*): the read loop then runs undisturbed -- 18.8-19.0 s for the 30x human job
@@ -483,7 +483,7 @@ class _ArenaPrefetch(object):
         if first_batch < 4096:
             return None                                  # a small job: one arena, sized by presize
         nbytes = engine.arena_bytes(first_batch, mean_length, error_rate) if hasattr(engine, 'arena_bytes') else arena_estimate(first_batch, mean_length, error_rate)
-        out_bytes = int(first_batch * (2.1 * mean_length + 400.0))
+        out_bytes = int(first_batch * (2.1 * mean_length + 400.0) * (1.0 + (PAF_SHARE if truth_paf else 0.0)))
         batches = -(-int(target_size) // max(int(first_batch * mean_length * max(world, 1)), 1))
         n = max(1, min(int(in_flight), batches))
         free, _ = torch.cuda.mem_get_info(engine.device)
@@ -505,10 +505,11 @@ class _BatchPool(object):
     batch is done (2 GB at HBM speed: ~1 ms) and gives the engine back at once; `depth` = in_flight + 2 batches may be outstanding,
     the surplus holding only their bytes."""
 
-    def __init__(self, engine, in_flight, arenas=None, device_gzip=False):
+    def __init__(self, engine, in_flight, arenas=None, device_gzip=False, truth_paf=False):
         import concurrent.futures
         import queue
         self.arenas = arenas
+        self.truth_paf = bool(truth_paf)                 # --truth-paf: every batch's truth alignments, made by its worker beside its FASTQ
         # --gzip-device: the worker of a batch that the stop rule cannot cut (submit(..., pack=True): the job still needs several
         # batches' worth of bases behind it) packs ITS batch on ITS engine's stream as soon as the batch is done and hands over
         # the gzip members instead of the text; the consumer packs only the job's last batches itself.  Round 5 packed every batch
@@ -612,13 +613,16 @@ class _BatchPool(object):
                 stream = self.streams[i]
                 eng = self.engines[i]
                 if n_mine == 0:
-                    return torch.zeros(0, dtype=torch.uint8), np.zeros(0, dtype=eng.stats_dtype)
+                    return torch.zeros(0, dtype=torch.uint8), np.zeros(0, dtype=eng.stats_dtype), None, None
                 if not self.on_gpu:
                     out, stats = eng.simulate_batch(seed, first, n_mine, allow_nofrag=True)
-                    return torch.from_numpy(np.ascontiguousarray(out).copy()), stats.copy()
+                    paf = eng.emit_paf_device(n_mine) if self.truth_paf else None
+                    return torch.from_numpy(np.ascontiguousarray(out).copy()), stats.copy(), None, paf
                 torch.cuda.set_device(eng.device)
                 with torch.cuda.stream(stream):
                     out, stats = eng.simulate_batch_device(seed, first, n_mine, allow_nofrag=True)
+                    # the truth alignments read what the batch left in the engine's arena: same job, same stream, before the engine is free
+                    paf = eng.emit_paf_device(n_mine) if self.truth_paf else None
                     stats = stats.copy()
                     packed = None
                     if pack and self.device_gzip and len(stats) and hasattr(eng, 'gzip_device'):
@@ -630,7 +634,7 @@ class _BatchPool(object):
                             packed = (nbytes, eng.gzip_device(out[:nbytes], blocks))      # a new tensor, made on this batch's stream
                     out = self._copy_of(torch, out) if packed is None else None   # the engine's buffer is free again; the copy runs on this batch's stream ...
                     stream.synchronize()                     # ... and is complete before the engine is handed to the next batch
-                    return (out, stats) if not self.device_gzip else (out, stats, packed)
+                    return out, stats, packed, paf
             finally:
                 with self.lock:
                     self.job_seconds += time.perf_counter() - t_job
@@ -654,7 +658,7 @@ class _BatchPool(object):
 
 
 def run_batches(engine, seed, target_size, mean_length, write, output, shard=None, max_batch=None, in_flight=1, device_gzip=False,
-                local_write=None, local_parts=None, expected_error=None, arenas=None):
+                local_write=None, local_parts=None, expected_error=None, arenas=None, truth_paf=False, paf_write=None):
     """
     The `while total_size < target_size` loop (simulate.py:63-86) over super-batches of read indices.
     `write(bytes_like)` receives the FASTQ bytes in read order on rank 0 only.  Returns (read count, total bases).
@@ -675,6 +679,10 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
     (its own PCIe link, its own file) and nothing travels to rank 0; `local_parts(n)` receives the byte count of every
     super-batch, which is what puts the ranks' files back into read order (batch by batch, rank after rank).  The
     exchange of 4 bytes per read and the stop rule are the same: the same reads are kept.
+
+    truth_paf (--truth-paf): every batch also yields its reads' truth alignments (engine.emit_paf_device), cut at the same
+    read as the FASTQ.  `paf_write` receives them in read order: on rank 0, over the same point-to-point exchange as the
+    FASTQ, or with local_write on every rank, its own reads' records (those of its own FASTQ file, in that file's order).
 
     A sink that fails on one rank of a multi-rank run (a full disk, a closed pipe) is reported in the same exchange -- one
     word per rank -- so that every rank leaves the loop at the same batch instead of waiting in a collective.
@@ -702,6 +710,8 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
         else:                                    # the job's identity law: arenas for Q30 reads are half those of 95 % reads
             engine.presize(first_batch, expected_mean, expected_error)
         out_bytes = int(first_batch * (engine.expected_record_bytes() if hasattr(engine, 'expected_record_bytes') else 2.1 * expected_mean + 400.0))
+        if truth_paf:                            # every batch in flight also holds its PAF text on the device
+            out_bytes = int(out_bytes * (1.0 + PAF_SHARE))
     else:
         out_bytes = 0
     asked = fit = max(1, int(in_flight))
@@ -713,7 +723,7 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
         fit = min(int(x[0]) for x in shard.gather_words(np.array([fit], dtype=np.uint32), [1] * shard.world))
     if fit < asked and shard.rank == 0:
         print(f'  {fit} of the {asked} batches in flight asked for fit into the free device memory', file=output)
-    pool = _BatchPool(engine, fit, arenas, device_gzip=device_gzip)
+    pool = _BatchPool(engine, fit, arenas, device_gzip=device_gzip, truth_paf=truth_paf)
     timing['create_engines'] = time.perf_counter() - t0
     ring = None
     if local_write is not None or shard.rank == 0:
@@ -725,6 +735,11 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
         #  wait_for_engine, profiles/r05b_cli_30x.json.  BRX_RING_PREALLOC=1 keeps the experiment reachable.)
         if pool.on_gpu and out_bytes and os.environ.get('BRX_RING_PREALLOC') and target_size > 3 * max_batch * expected_mean:
             ring.prealloc(int(1.25 * out_bytes))
+    paf_ring = None
+    if truth_paf and paf_write is not None:
+        paf_ring = _HostRing(torch, pinned=pool.on_gpu)      # the PAF text leaves through its own ring and writer thread
+        paf_ring.sink = paf_write
+        paf_ring.defer_errors = shard.world > 1
     sink_failed_on = None
 
     def staging(nbytes):
@@ -765,7 +780,7 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
             _, fut, base, n_super, first, n_mine = pending.popleft()
             t0 = time.perf_counter()
             res = fut.result()
-            out, stats, prepacked = res if len(res) == 3 else (res[0], res[1], None)
+            out, stats, prepacked, paf = res
             timing['wait_for_batch'] += time.perf_counter() - t0
             timing['batches'] += 1
             # ---- the 4 B/read exchange: length (0 for skipped reads) | NOFRAG << 31 | BAD << 30 ----
@@ -775,7 +790,8 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
             words |= np.where(stats['status'] & BAD_STATUS, FLAG_BAD, 0).astype(np.uint32)
             per_rank = [Shard(r, shard.world).slice_of(base, n_super)[1] for r in range(shard.world)]
             if shard.world > 1:                     # one more word per rank: "my sink has failed"
-                mine = np.append(words, np.uint32(1 if ring is not None and ring.error is not None else 0))
+                failed_here = any(x is not None and x.error is not None for x in (ring, paf_ring))     # the FASTQ's sink or the PAF's
+                mine = np.append(words, np.uint32(1 if failed_here else 0))
                 parts = shard.gather_words(mine, [c + 1 for c in per_rank])
                 failed = [r for r, part in enumerate(parts) if part[-1]]
                 if failed:
@@ -840,6 +856,16 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
             else:
                 for _, part in shard.collect_bytes(out, sizes, staging):
                     ring.write(part)                # rank 0: through pinned memory to the writer thread
+            if truth_paf:                           # the records of the same reads, the same way
+                paf_bytes = int(paf[1][keep]) if paf is not None else 0
+                if local_write is not None or shard.world == 1:
+                    if paf_bytes and paf_ring is not None:
+                        paf_ring.write(paf[0][:paf_bytes])
+                else:
+                    paf_sizes = [int(x[0]) for x in shard.gather_words(np.array([paf_bytes], dtype=np.uint32), [1] * shard.world)]
+                    assert paf_bytes < 2 ** 32
+                    for _, part in shard.collect_bytes(paf[0] if paf is not None else None, paf_sizes, staging):
+                        paf_ring.write(part)
             timing['copy_out'] += time.perf_counter() - t0
             if shard.rank == 0:
                 print_progress(count, total, target_size, output)
@@ -878,6 +904,8 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
             ring.flush(reraise=sys.exc_info()[0] is None and sink_failed_on is None and not ring.defer_errors)
             timing['sink'] = ring.sink_seconds
             timing['ring_alloc'] = ring.alloc_seconds
+        if paf_ring is not None:
+            paf_ring.flush(reraise=sys.exc_info()[0] is None and sink_failed_on is None and not paf_ring.defer_errors)
         timing['flush'] = time.perf_counter() - t0
         timing['retries'] = sum(getattr(e, 'retries', 0) for e in pool.engines if e is not None)
         timing['device_batch_seconds_avg'] = pool.job_seconds / max(pool.job_count, 1.0)
@@ -892,6 +920,8 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
         print('\n', file=output)
     if ring is not None and ring.error is not None and (sink_failed_on is not None or ring.defer_errors):
         raise ring.error                     # this rank's own sink
+    if paf_ring is not None and paf_ring.error is not None and (sink_failed_on is not None or paf_ring.defer_errors):
+        raise paf_ring.error                 # this rank's own PAF file
     if sink_failed_on is not None:
         sys.exit(f'Error: the output of rank {sink_failed_on} failed; every rank stopped at the same batch')
     if fatal:
@@ -980,7 +1010,8 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
     mark('reference_on_device')
     # the job's arenas from now on, beside everything below (models, tables, the first batch): _ArenaPrefetch
     arenas = _ArenaPrefetch.for_job(engine, get_target_size(pref.n_bases, args.quantity), float(args.mean_frag_length),
-                                    expected_error_rate(identities), getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, shard.world)
+                                    expected_error_rate(identities), getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, shard.world,
+                                    truth_paf=bool(getattr(args, 'truth_paf', None)))
     # a model file that is not in the cache is aligned (align_kmers, error_model.py:179-229) on THIS engine
     error_model = ErrorModel(args.error_model, quiet, aligner=lambda qs, ts: engine.align_batch(qs, ts)[0])
     qscore_model = QScoreModel(args.qscore_model, quiet)
@@ -1055,11 +1086,26 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
             log.wrote(len(part))
 
         local_parts = log.batch
+    # --truth-paf PATH: the truth alignments of the reads (brx_emit_paf), plain text; with --output-shards every rank writes
+    # PATH.<rank>, the records of the reads of its own FASTQ file
+    truth_paf = getattr(args, 'truth_paf', None)
+    paf_write = None
+    if truth_paf:
+        if not hasattr(engine, 'emit_paf_device'):
+            shard.finish()
+            sys.exit('Error: --truth-paf needs the GPU engine')
+        if prefix or shard.rank == 0:
+            paf_file = open(f'{truth_paf}.{shard.rank}' if prefix else truth_paf, 'wb')
+            files.append(paf_file)
+
+            def paf_write(part):
+                paf_file.write(part)
     try:
         try:
             result = run_batches(engine, seed, target_size, float(args.mean_frag_length), write, quiet, shard,
                                  in_flight=getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, device_gzip=device_gzip,
-                                 local_write=local_write, local_parts=local_parts, expected_error=expected_error_rate(identities), arenas=arenas)
+                                 local_write=local_write, local_parts=local_parts, expected_error=expected_error_rate(identities), arenas=arenas,
+                                 truth_paf=bool(truth_paf), paf_write=paf_write)
             if prefix and hasattr(shard_sink, 'flush') and shard_sink is not shard_file:
                 shard_sink.flush()
         finally:

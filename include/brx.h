@@ -350,6 +350,15 @@ size_t brx_gzip_device_scratch(size_t n_bytes, uint32_t n_blocks);
 int brx_gzip_device(brx_ctx *ctx, const void *d_in, size_t n_bytes, const uint64_t *d_block_off, uint32_t n_blocks, void *d_out,
                     size_t out_cap, void *d_scratch, size_t scratch_bytes, size_t *out_bytes, void *hip_stream);
 
+/* ---- truth alignments: where every base of the simulated reads came from, as PAF text ----
+ * Truth alignments (PAF text) of the reads of the LAST brx_simulate_batch on ctx; valid until the next pipeline call on ctx
+ * (BRX_E_STATE otherwise, and after brx_sequence_fragments / brx_align_batch / brx_model_count).  Records back to back in
+ * read order; d_read_off (device, n_reads + 1 u64, may be NULL) receives each read's start, the last entry = *out_bytes.
+ * BRX_E_OUTPUT + brx_output_needed() when out_cap is too small (nothing written; the call may be repeated).  Synchronous.
+ * A record is a maximal run of alignment columns whose fragment bases come from one contig and strand, consecutively, and
+ * whose read bases are all in the FASTQ read, trimmed to its first and last =/X column (README: --truth-paf). */
+int brx_emit_paf(brx_ctx *ctx, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
