@@ -149,14 +149,22 @@ def recipe_fragment(seed, length, with_n=False):
     return codes
 
 
+def case_fragment(c):
+    """The fragment of a digest case: the uniform recipe above, or -- a case with a 'kind' -- tests/lowcomplexity.py's."""
+    if c.get('kind'):
+        import lowcomplexity
+        return lowcomplexity.codes(c['kind'], c['seed'], c['length'], c['with_n'])
+    return recipe_fragment(c['seed'], c['length'], c['with_n'])
+
+
 def check_digest_cases(engine_of, cases):
     """Every digest case through `engine_of(em, qm)` (an engine configured with that model pair): sha256 of the sequence and of the
     qualities, the identity as the same double, the loop count."""
     import hashlib
     for c in cases:
         eng = engine_of(c['em'], c['qm'])
-        res, st = eng.sequence_fragments(c['seed'], c['read'], [recipe_fragment(c['seed'], c['length'], c['with_n'])], [c['target']])
-        tag = (c['em'], c['length'], c['target'], c['seed'])
+        res, st = eng.sequence_fragments(c['seed'], c['read'], [case_fragment(c)], [c['target']])
+        tag = (c['em'], c.get('kind', 'uniform'), c['length'], c['target'], c['seed'])
         seq = ''.join('ACGTN'[x] for x in res[0][0])
         assert len(seq) == c['seq_len'] and hashlib.sha256(seq.encode()).hexdigest() == c['seq_sha256'], tag
         assert hashlib.sha256(res[0][1].tobytes()).hexdigest() == c['qual_sha256'], tag

@@ -187,6 +187,36 @@ def test_sequence_fragment_digest_cases_bound_the_power_difference():
     assert p15['doubles'] == 10_000_000 and p15['largest_difference_ulps'] <= 1 and p15['differ'] == round(p15['rate'] * p15['doubles'])
 
 
+def test_sequence_fragment_digest_cases_on_low_complexity_fragments():
+    """Parity layer 2 on sequence no other fixture holds: tests/golden/sequence_fragment_lowcomplexity.json.gz -- the UNMODIFIED
+    sequence_fragment replayed with our draws (tools/make_golden.py sequence_fragment_lowcomplexity) on the fragments of
+    tests/lowcomplexity.py: every kind under seven model pairs, lengths 999 / 1000 / 1001, 2-12 kb, four period-2 fragments of
+    50 kb, some with N.  Co-optimal alignments everywhere: the reference's path through them (the aligner shim's canonical
+    tie-break) decides the identity the loop stops on and every CIGAR window of the qscores.  The oracle reproduces every case."""
+    import lowcomplexity as LC
+    g = load('sequence_fragment_lowcomplexity.json.gz')
+    cases = g['cases']
+    assert len(cases) >= 200
+    assert {c['kind'] for c in cases} == set(LC.KINDS)
+    assert {(c['em'], c['qm']) for c in cases} >= {('nanopore2023', 'nanopore2023'), ('nanopore2018', 'nanopore2018'),
+                                                   ('nanopore2020', 'nanopore2020'), ('pacbio2016', 'pacbio2016'),
+                                                   ('pacbio2021', 'pacbio2021'), ('random', 'random'), ('random', 'ideal')}
+    assert {999, 1000, 1001} <= {c['length'] for c in cases}
+    assert sum(c['length'] == 50000 and c['kind'] == 'tandem2' for c in cases) >= 3
+    assert sum(2000 <= c['length'] <= 12000 for c in cases) >= 100 and sum(c['with_n'] for c in cases) >= 20
+    assert all(0.78 <= c['target'] <= 0.99 for c in cases)
+    engines = {}
+
+    def engine_of(em, qm):
+        if (em, qm) not in engines:
+            e = H.oracle_engine()
+            e.set_error_model(ErrorModel(em, NULL).tables())
+            e.set_qscore_model(QScoreModel(qm, NULL).tables())
+            engines[(em, qm)] = e
+        return engines[(em, qm)]
+    H.check_digest_cases(engine_of, cases)
+
+
 # ------------------------------------------------------------------------------------------------
 CIGAR = '=XID'
 
@@ -226,6 +256,48 @@ def test_aligner_myers_equals_full_dp():
         qn = int((o1 != 3).sum())
         tn = int((o1 != 2).sum())
         assert qn == len(q) and tn == len(t)
+
+
+def test_aligner_myers_equals_full_dp_on_low_complexity_pairs():
+    """Parity layer 4 where co-optimal paths are everywhere: every kind of tests/lowcomplexity.py at every size of the list above
+    (12 kinds x 11 sizes, the two counters coprime), both argument orders; the target a mutated copy, or -- one pair in seven --
+    another text of the same kind and another length.  Block Myers and the full matrix must agree on the distance and on the
+    whole canonical path (I, then D, then diagonal)."""
+    import lowcomplexity as LC
+    rng = np.random.default_rng(13)
+    sizes = [1, 2, 7, 31, 32, 33, 64, 65, 100, 257, 700]
+    pairs = 0
+    for it in range(3 * len(LC.KINDS) * len(sizes)):
+        kind, n = LC.KINDS[it % len(LC.KINDS)], sizes[it % len(sizes)]
+        q = LC.text(kind, it, n)
+        t = H.mutate_seq(rng, q, float(rng.choice([0, 0.02, 0.1, 0.3, 0.6]))) or 'A'
+        if it % 7 == 0:
+            t = LC.text(kind, it + 1, int(rng.integers(1, 2 * n + 2)))
+        for a, b in ((q, t), (t, q)):
+            d1, o1 = pyoracle.align(a.encode(), b.encode())
+            d2, o2 = pyoracle.align(a.encode(), b.encode(), dp=True)
+            assert d1 == d2 and H.first_diff(o1, o2) < 0, (kind, a, b)
+            assert int((o1 != 3).sum()) == len(a) and int((o1 != 2).sum()) == len(b)
+            pairs += 1
+    assert pairs >= 400
+
+
+def test_aligner_band_hint_does_not_change_the_path_on_a_period_2_repeat():
+    """... where the canonical path strays from the straight line by several times what a uniform pair of the same distance does:
+    any proven bound gives the path of the unbounded call, and a bound below the distance is refused."""
+    import lowcomplexity as LC
+    rng = np.random.default_rng(14)
+    q = LC.text('tandem2', 4, 3600)
+    t = H.mutate_seq(rng, q, 0.08)
+    d, ops = pyoracle.align(q.encode(), t.encode())
+    assert d > 100
+    for a, b in ((q, t), (t, q)):
+        d1, o1 = pyoracle.align(a.encode(), b.encode())
+        assert d1 == d
+        for k in (d, d + 1, 2 * d, len(a)):
+            d2, o2 = pyoracle.align(a.encode(), b.encode(), k=k)
+            assert d2 == d and H.first_diff(o1, o2) < 0, k
+        assert pyoracle.align(a.encode(), b.encode(), k=d - 1)[0] < 0
 
 
 def test_aligner_band_hint_does_not_change_the_path():

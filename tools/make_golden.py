@@ -28,6 +28,10 @@ Fixtures written (each records reference version + how it was produced):
                        bounds, est**1.5, the 25-change alignment cadence and blending, trimming,
                        cigar windows and the fallback rule -- is executed by the reference.  The
                        oracle (and the HIP path) must reproduce seq / quals / identity exactly.
+  sequence_fragment_bound.json.gz, sequence_fragment_lowcomplexity.json.gz
+                       the same replay kept as digests with the recipe of the fragment: 524 uniform
+                       fragments, and 204 low-complexity ones (tests/lowcomplexity.py: homopolymers,
+                       tandem repeats, diverged arrays, two letters, splices with N runs).
 
 Run:  python tools/make_golden.py        (needs /root/reference; ~1 minute)
 """
@@ -550,16 +554,21 @@ def _bound_case(spec):
     """One digest case (a worker process of make_sequence_fragment_bound)."""
     import hashlib
     import helpers as H
-    em_name, qm_name, length, target, seed, read, with_n = spec
+    em_name, qm_name, length, target, seed, read, with_n = spec[:7]
+    kind = spec[7] if len(spec) > 7 else None            # a low-complexity case: the recipe is tests/lowcomplexity.py's
     engine = H.oracle_engine()
     engine.set_error_model(ErrorModel(em_name, NULL).tables())
     qtables = QScoreModel(qm_name, NULL).tables()
     engine.set_qscore_model(qtables)
     random.seed(12345)
     ref_qmodel = ref_qm.QScoreModel(qm_name, NULL)
-    fragment = recipe_fragment(seed, length, with_n)
+    if kind:
+        import lowcomplexity
+        fragment = lowcomplexity.text(kind, seed, length, with_n)
+    else:
+        fragment = recipe_fragment(seed, length, with_n)
     c = replay_sequence_fragment(engine, em_name, qm_name, ref_qmodel, qtables, fragment, target, seed=seed, read=read)
-    return {'em': em_name, 'qm': qm_name, 'length': length, 'with_n': with_n, 'target': target, 'seed': seed, 'read': read,
+    return {**({'kind': kind} if kind else {}), 'em': em_name, 'qm': qm_name, 'length': length, 'with_n': with_n, 'target': target, 'seed': seed, 'read': read,
             'seq_len': len(c['seq']), 'seq_sha256': hashlib.sha256(c['seq'].encode()).hexdigest(),
             'qual_sha256': hashlib.sha256(c['qual'].encode()).hexdigest(), 'identity': c['identity'],
             'identity_by_qscores': c['identity_by_qscores'], 'iterations': c['iterations'], 'alignments': c['alignments']}
@@ -603,6 +612,39 @@ def make_sequence_fragment_bound():
                                 'applied change moves `errors` by ~1e-16 relative -- it changes a result only if it flips one of the '
                                 'comparisons est <= target / the rounded identity of a later alignment: none of the replays above did'})
     print(f'  pow15: {differ} of {n} differ ({differ / n:.3%}), at most {worst} ulp')
+
+
+LOWCOMPLEXITY_MODELS = (('nanopore2023', 'nanopore2023'), ('nanopore2018', 'nanopore2018'), ('nanopore2020', 'nanopore2020'),
+                        ('pacbio2016', 'pacbio2016'), ('pacbio2021', 'pacbio2021'), ('random', 'random'), ('random', 'ideal'))
+
+
+def make_sequence_fragment_lowcomplexity():
+    """The same replay and digest format as sequence_fragment_bound on the fragments of tests/lowcomplexity.py: homopolymer
+    mosaics, tandem repeats of period 1-6, diverged arrays (a 171-mer among them), a two-letter alphabet and splices with N runs.
+    Every kind under every model pair (12 kinds x 7 pairs: the two counters are coprime), targets 0.78-0.99, lengths at the
+    edges of ALIGNMENT_SIZE (999 / 1000 / 1001), below it, 2-12 kb, and four period-2 fragments of 50 kb -- the input on which
+    the canonical path of the final alignment strays furthest from the straight line; one case in six has one base in 256
+    replaced by N.  A case keeps its 'kind': helpers.case_fragment rebuilds the fragment."""
+    import multiprocessing
+    import lowcomplexity
+    rng = random.Random(91)
+    specs = []
+    for i in range(4):
+        specs.append(('nanopore2023', 'nanopore2023', 50000, round(rng.uniform(0.80, 0.92), 3), 8000 + i, 19 * i + 2, False, 'tandem2'))
+    for i in range(200):
+        em_name, qm_name = LOWCOMPLEXITY_MODELS[i % 7]
+        if i % 10 == 0:
+            length = (999, 1000, 1001)[(i // 10) % 3]
+        elif i % 10 == 5:
+            length = rng.randint(30, 900)
+        else:
+            length = rng.randint(2000, 12000)
+        specs.append((em_name, qm_name, length, round(rng.uniform(0.78, 0.99), 3), 9000 + i, 17 * i + 7, i % 6 == 0,
+                      lowcomplexity.KINDS[i % len(lowcomplexity.KINDS)]))
+    with multiprocessing.Pool(min(8, os.cpu_count() or 1)) as pool:
+        cases = pool.map(_bound_case, specs, chunksize=2)
+    dump('sequence_fragment_lowcomplexity.json.gz', {'cases': cases})
+    print(f'  {len(cases)} digest cases, {sum(c["iterations"] for c in cases)} loop iterations, {sum(c["alignments"] for c in cases)} alignments')
 
 
 def make_random_change():
@@ -753,6 +795,9 @@ if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'sequence_fragment_bound':
         make_sequence_fragment_bound()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'sequence_fragment_lowcomplexity':
+        make_sequence_fragment_lowcomplexity()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'sequence_fragment':
         make_sequence_fragment()
         sys.exit(0)
@@ -768,3 +813,4 @@ if __name__ == '__main__':
     make_qscore_top_rows()
     make_model_builders()
     make_sequence_fragment_bound()
+    make_sequence_fragment_lowcomplexity()
