@@ -150,7 +150,11 @@ def recipe_fragment(seed, length, with_n=False):
 
 
 def case_fragment(c):
-    """The fragment of a digest case: the uniform recipe above, or -- a case with a 'kind' -- tests/lowcomplexity.py's."""
+    """The fragment of a digest case: the uniform recipe above, or -- a case with a 'kind' -- tests/lowcomplexity.py's, or
+    tests/custom_models.py's slices of its template (the kind 'template')."""
+    if c.get('kind') == 'template':
+        import custom_models
+        return custom_models.fragment_codes(c['seed'], c['length'], c['with_n'])
     if c.get('kind'):
         import lowcomplexity
         return lowcomplexity.codes(c['kind'], c['seed'], c['length'], c['with_n'])

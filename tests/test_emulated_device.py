@@ -234,20 +234,15 @@ def test_window_overflow_goes_through_the_whole_read_kernel(tmp_path, route, mon
 
 
 def _window_overflow(tmp_path, defines=()):
-    """A synthetic error model whose alternatives insert 60 bases: the joined 1000-base windows outgrow their pass slots
+    """A synthetic error model whose alternatives insert 60 bases (tests/custom_models.py: e3_big): the joined 1000-base windows outgrow their pass slots
     (BRX_WIN_TMAX), so those reads are handed to the whole-read kernel k_mutate with inline alignments -- a route no
     packaged model reaches.  Mutated reads of 17x the fragment length also push the final alignment into the widest
     band classes (8 and 16 words per lane)."""
     import io
-    import itertools
+    import custom_models
     from badread_amd.error_model import ErrorModel
     rng = np.random.default_rng(4)
-    lines = []
-    for kmer in map(''.join, itertools.product('ACGT', repeat=3)):
-        ins = ''.join(rng.choice(list('ACGT'), 60))
-        lines.append(f'{kmer},0.2;{kmer[0]}{kmer[1]}{ins}{kmer[2]},0.6;{kmer[0]}{kmer[2]},0.2;\n')
-    path = tmp_path / 'big_insertions_model'
-    path.write_text(''.join(lines))
+    path = custom_models.write('e3_big', tmp_path / 'big_insertions_model')       # (tests/golden/models/e3_big holds the same text)
     tables = ErrorModel(str(path), io.StringIO(), aligner=pyoracle.oracle_align_batch, use_cache=False).tables()
     pref, _ = H.small_reference()
     import emu_engine as EE

@@ -32,6 +32,9 @@ Fixtures written (each records reference version + how it was produced):
                        the same replay kept as digests with the recipe of the fragment: 524 uniform
                        fragments, and 204 low-complexity ones (tests/lowcomplexity.py: homopolymers,
                        tandem repeats, diverged arrays, two letters, splices with N runs).
+  models/*, sequence_fragment_custom_models.json.gz
+                       synthetic error- and qscore-model FILES (tests/custom_models.py: nothing in them comes from the
+                       reference) and the same replay under them: the reference loads the files itself.
 
 Run:  python tools/make_golden.py        (needs /root/reference; ~1 minute)
 """
@@ -562,7 +565,10 @@ def _bound_case(spec):
     engine.set_qscore_model(qtables)
     random.seed(12345)
     ref_qmodel = ref_qm.QScoreModel(qm_name, NULL)
-    if kind:
+    if kind == 'template':                               # a custom-model case: slices of tests/custom_models.py's template
+        import custom_models
+        fragment = custom_models.fragment_text(seed, length, with_n)
+    elif kind:
         import lowcomplexity
         fragment = lowcomplexity.text(kind, seed, length, with_n)
     else:
@@ -644,6 +650,45 @@ def make_sequence_fragment_lowcomplexity():
     with multiprocessing.Pool(min(8, os.cpu_count() or 1)) as pool:
         cases = pool.map(_bound_case, specs, chunksize=2)
     dump('sequence_fragment_lowcomplexity.json.gz', {'cases': cases})
+    print(f'  {len(cases)} digest cases, {sum(c["iterations"] for c in cases)} loop iterations, {sum(c["alignments"] for c in cases)} alignments')
+
+
+def make_custom_model_files():
+    """tests/golden/models/*: the synthetic model files of tests/custom_models.py (pure functions of their names)."""
+    import custom_models
+    os.makedirs(custom_models.MODEL_DIR, exist_ok=True)
+    for name in custom_models.NAMES:
+        path = custom_models.write(name, custom_models.path_of(name))
+        print(f'models/{name}: {os.path.getsize(path)} bytes')
+
+
+def make_sequence_fragment_custom_models():
+    """The same replay and digest format as sequence_fragment_bound under the model FILES of tests/golden/models/ (written
+    first: make_custom_model_files): every error model with q9_gap4 and q1, every qscore model with e9_sparse and nanopore2023,
+    on fragments cut from the template the sparse models are made of (custom_models.DIGEST_SPECS: lengths 30, 999 / 1000 / 1001
+    and 1500-3000, targets 0.6-0.99).  `em` and `qm` of a case are file names relative to tests/golden/models/, so the replay runs
+    with that folder as the working directory: the reference loads the same files by the same names, and aligns every alternative
+    through oracle/shim/edlib as everywhere in this generator (tests/custom_models.py says which inner alignments are unique).
+    Our side's inner alignments come from the oracle's aligner, through a cache folder of its own that the worker processes read.
+    ReplayQScoreModel asserts that every cigar the reference finds has a row in our table.  The reference loaded and ran every
+    model: none was dropped."""
+    import multiprocessing
+    import tempfile
+    import custom_models
+    make_custom_model_files()
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as cache:
+        os.environ['BADREAD_AMD_CACHE'] = cache
+        os.chdir(custom_models.MODEL_DIR)
+        try:
+            for name in custom_models.ERROR_MODELS:
+                ErrorModel(name, NULL, aligner=pyoracle.oracle_align_batch)
+            with multiprocessing.Pool(min(8, os.cpu_count() or 1)) as pool:
+                cases = pool.map(_bound_case, custom_models.DIGEST_SPECS, chunksize=2)
+        finally:
+            os.chdir(cwd)
+            del os.environ['BADREAD_AMD_CACHE']
+    dump('sequence_fragment_custom_models.json.gz', {'cases': cases})
     print(f'  {len(cases)} digest cases, {sum(c["iterations"] for c in cases)} loop iterations, {sum(c["alignments"] for c in cases)} alignments')
 
 
@@ -798,6 +843,9 @@ if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'sequence_fragment_lowcomplexity':
         make_sequence_fragment_lowcomplexity()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'sequence_fragment_custom_models':
+        make_sequence_fragment_custom_models()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'sequence_fragment':
         make_sequence_fragment()
         sys.exit(0)
@@ -814,3 +862,4 @@ if __name__ == '__main__':
     make_model_builders()
     make_sequence_fragment_bound()
     make_sequence_fragment_lowcomplexity()
+    make_sequence_fragment_custom_models()
