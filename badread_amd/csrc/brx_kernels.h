@@ -46,7 +46,7 @@ struct RS {
     uint32_t end_trim, seg_off, piece_off, n_cols;
     uint32_t n_match, loops, changes, naligns;
     uint32_t seq_len, rec_len, hdr_len, klass;     /* klass: band class of the final alignment (words per lane) | BRX_KL_RETRY, set by k_fin_join */
-    uint64_t F_off, seq_off, ops_off, units, tb_off, rec_off;
+    uint64_t F_off, seq_off, ops_off, units, tb_off, rec_off;     /* tb_off: unused (rounds 1-5: the read's col_of[]); kept for the layout */
     double target, qerr;
 };
 
@@ -899,13 +899,6 @@ __global__ void __launch_bounds__(64) k_scan_mut(uint32_t n, RS *rs, const uint3
     if (lane == 0) { totals[0] = seq_run << 4; totals[1] = ops_run << 4; }
 }
 
-/* rs[order[i]].tb_off = off[i] (and .units = units[i] when given): the host lays traceback stores out in
-   processing order; the retry phase also replaces the windowed sizes by full-band sizes */
-__global__ void __launch_bounds__(64) k_set_tboff(uint32_t n, RS *rs, const uint32_t *order, const uint64_t *off, const uint64_t *units) {
-    uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    if (i < n) { rs[order[i]].tb_off = off[i]; if (units) rs[order[i]].units = units[i]; }
-}
-
 /* =============================================================================================
  * final stage: the tail of sequence_fragment (simulate.py:348-356) and get_qscores
  * (qscore_model.py:32-75): join the mutated read, align it against the perfect fragment, walk the
@@ -981,7 +974,7 @@ __global__ void __launch_bounds__(64) k_fin_join(BrxDev d, RS *rs, const uint32_
             /* ... and a band of up to 13 superblocks of one or two words four reads per wave, a row of 16 lanes each */
             const bool quad = fin_quad && !lanes && acgt && g.G == 1 && (brx_quad_words(s.m, s.n, s.ub) & fin_quad) != 0;
             o->klass = (g.G ? (uint32_t)g.G : 0xFFFFu) | (junk ? BRX_KL_FULL : 0u) | (lanes ? BRX_KL_LANES : 0u) | (quad ? BRX_KL_QUAD : 0u);
-            o->units = brx_final_units(s.m, s.n, s.ub, junk ? 0 : d.tb_hmul, &too_wide);     /* traceback store + col_of[] */
+            o->units = brx_final_units(s.m, s.n, s.ub, junk ? 0 : d.tb_hmul, &too_wide);     /* traceback store */
             if (too_wide) o->status = s.status | BRX_RS_BAND;
         }
     }
@@ -1085,7 +1078,7 @@ __global__ void __launch_bounds__(64, 4) k_fin_quad(BrxDev d, RS *rs, const uint
 }
 
 /* One band class of one set: `list` holds the class's reads (longest first), `ctr` is the 64-bit counter of the slab scheme
-   (brx_hip.hip, launch_final_phase): low half = list position, high half = waves that have started.  A wave's first pop adds
+   (brx_finplan.h, brx_plan_final): low half = list position, high half = waves that have started.  A wave's first pop adds
    to both halves at once -- its ticket t is then at most the position it popped -- and slab t (slabs[t] .. slabs[t + 1], in
    8-byte units from slab_base) holds the traceback store of every read the wave will ever pop. */
 #ifndef BRX_FIN4_WAVES
@@ -1142,7 +1135,7 @@ __global__ void __launch_bounds__(64, (MAXG == 1 ? BRX_FIN1_WAVES : MAXG == 2 ? 
 #define BRX_QS_PEND 128          /* power of two, at least 127: up to 63 windows wait while 64 more arrive */
 __global__ void __launch_bounds__(64) k_fin_qscore(BrxDev d, RS *rs, const uint32_t *order, uint32_t q_begin, uint32_t q_end,
                                                     uint32_t *queue, int phase, int klo, int khi, uint8_t *seqbuf, const uint8_t *opsbuf,
-                                                    uint8_t *tb_base, uint64_t *clk) {
+                                                    uint64_t *clk) {
     __shared__ uint32_t qhist[256];
     __shared__ uint32_t hot_thr[BRX_QS_HOT_MAX], hot_score[BRX_QS_HOT_MAX];
     __shared__ uint8_t hot_idx[256];

@@ -305,7 +305,7 @@ def test_four_final_alignments_per_wave(case, monkeypatch):
 @pytest.mark.parametrize('quad,small', [(0, 10 << 20), (1, 0)])
 def test_final_stage_with_fewer_slabs_than_reads(quad, small, monkeypatch):
     """The traceback stores of the final stage are slabs owned by the waves of the align kernels, sized by queue position
-    (brx_hip.hip, launch_final_phase).  An arena that holds the largest store but not one slab per read (per group of four reads
+    (brx_finplan.h, brx_plan_final).  An arena that holds the largest store but not one slab per read (per group of four reads
     with k_fin_quad): the set runs with fewer waves, every wave reusing its slab for several reads; same bytes.  (10 MB: the mutate
     stage's top region -- 29 window slots of 128 KB; an all-head batch has no lane stores and no rings -- and the batch's strings fit,
     16 slabs of the final stage do not: 8 are used.  Round 5's layout kept the mutate buffers beside the slabs and needed 20 MB for that.)"""
