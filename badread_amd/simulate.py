@@ -19,9 +19,16 @@ read indices (brx_simulate_batch, include/brx.h); this module keeps what stays o
 Randomness: every draw on the device is Philox4x32-10 keyed by (seed, read index, stream)
 (include/brx_spec.h), so a seed fixes the output bytes, but not to the reference's MT19937 stream.
 """
+import collections
+import concurrent.futures
+import contextlib
+import gzip
+import math
 import os
+import queue
 import random
 import sys
+import threading
 import time
 
 import numpy as np
@@ -212,7 +219,7 @@ class Shard(object):
         a rank that then tears its connections down while a peer is still flushing makes gloo abort the peer, so the ranks
         meet once more and the group this object created is destroyed in order."""
         if self.world > 1 and self.dist is not None and self.dist.is_initialized():
-            self.gather_words(np.zeros(1, dtype=np.uint32), [1] * self.world)
+            self.gather_word(0)
             if self.owns_group:
                 self.dist.destroy_process_group()
                 self.owns_group = False
@@ -272,6 +279,10 @@ class Shard(object):
         self.dist.all_gather(parts, mine)
         return [p[:n].cpu().numpy().view(np.uint32) for p, n in zip(parts, counts)]
 
+    def gather_word(self, v):
+        """One uint32 of every rank, as a list of ints in rank order."""
+        return [int(x[0]) for x in self.gather_words(np.array([v], dtype=np.uint32), [1] * self.world)]
+
     def collect_bytes(self, mine, sizes, staging):
         """Record bytes to rank 0, point to point: rank r > 0 sends its `sizes[r]` bytes (a device tensor over RCCL /
         xGMI in production, a CPU tensor over gloo in the tests) and rank 0 receives them in rank order into `staging`.
@@ -293,6 +304,7 @@ class Shard(object):
 
 FLAG_NOFRAG, FLAG_BAD = 1 << 31, 1 << 30          # status bits packed beside the read length in the 4 B/read gather
 BAD_STATUS = RS_TOO_MANY_SEGS | RS_BAND | RS_QMISS
+_Pending = collections.namedtuple('_Pending', 'future base n_super first n_mine')      # an issued super-batch [base, base + n_super) and this rank's slice of it
 
 
 def cut_point(seq_lens, running_total, target_size):
@@ -314,50 +326,85 @@ def plan_batch(remaining_bases, mean_length, world, max_batch):
     return per_rank * world
 
 
+def exchange_words(stats):
+    """A batch's 4 B/read for the exchange between ranks: length (0 for skipped reads) | NOFRAG << 31 | BAD << 30."""
+    words = (stats['seq_len'].astype(np.uint32) * (stats['rec_len'] > 0)).astype(np.uint32)
+    assert not len(words) or int(words.max()) < FLAG_BAD
+    words |= np.where(stats['status'] & RS_NOFRAG, FLAG_NOFRAG, 0).astype(np.uint32)
+    words |= np.where(stats['status'] & BAD_STATUS, FLAG_BAD, 0).astype(np.uint32)
+    return words
+
+
+def stop_decision(allw, base, total, target_size):
+    """(last, fatal, bad_read) from every rank's words of the super-batch starting at read `base`, `total` bases consumed before it.  `last`: batch
+    position of the last read kept: the one reaching the target, or the one before an earlier flagged read (NOFRAG: `fatal`, else `bad_read`), or the end."""
+    lens = (allw & (FLAG_BAD - 1)).astype(np.int64)
+    cut = cut_point(lens, total, target_size)
+    wrong = np.flatnonzero(allw & (FLAG_NOFRAG | FLAG_BAD))
+    if len(wrong) and (cut is None or wrong[0] < cut):
+        stop_at = int(wrong[0])
+        nofrag = bool(allw[stop_at] & FLAG_NOFRAG)
+        return stop_at - 1, nofrag, None if nofrag else base + stop_at
+    return (cut if cut is not None else len(allw) - 1), False, None
+
+
+def kept_bytes(stats, first, base, last, n_mine):
+    """(keep, my_bytes): how many of this rank's reads [first, first + n_mine) have a batch position <= last, and their FASTQ bytes."""
+    keep = int(np.clip(last - (first - base) + 1, 0, n_mine))
+    return keep, (int(stats['rec_off'][keep - 1] + stats['rec_len'][keep - 1]) if keep else 0)
+
+
+def expected_out_bytes(engine, n_reads, mean_length, truth_paf):
+    """Bytes a batch of `n_reads` reads is expected to leave on the device (with --truth-paf its PAF text too): by the engine's estimate
+    from its parameters, or at 2.1 B per base + 400 per read for an engine without one (None: its parameters are not set yet)."""
+    per_read = engine.expected_record_bytes() if hasattr(engine, 'expected_record_bytes') else 2.1 * mean_length + 400.0
+    out_bytes = int(n_reads * per_read)
+    return int(out_bytes * (1.0 + PAF_SHARE)) if truth_paf else out_bytes
+
+
+def driver_reserve_bytes():
+    """Device memory left to the runtime's own allocations (engines_for_memory)."""
+    return int(float(os.environ.get('BRX_DRIVER_RESERVE_GB', '24')) * (1 << 30))
+
+
+def engines_for_memory(free, wanted, arena_bytes, arenas_held, out_bytes, reserve):
+    """How many of `wanted` engines fit into `free` bytes of device memory, at least one: n - arenas_held more arenas, n output buffers and
+    n + 2 copies of a batch's bytes waiting for the consumer, beside `reserve` for what the runtime allocates on its own -- the private segments
+    of the planning kernels (1.6 KB per lane, per hardware queue: ~0.9 GB each over the ~20 queues of a six-engine job), the gzip stage, other
+    ranks' records on rank 0.  A job that asks for more runs on fewer (six 65536-read engines with 40 GB arenas died with
+    HSA_STATUS_ERROR_OUT_OF_RESOURCES at the edge of the 288 GB, where no allocation of ours failed)."""
+    n = wanted
+    while n > 1 and (n - arenas_held) * arena_bytes + (2 * n + 2) * out_bytes + reserve > free:
+        n -= 1
+    return n
+
+
+def _on_gpu(engine):
+    """The engine computes on a GPU (the tests' CPU checker engines have no `device`)."""
+    return getattr(getattr(engine, 'device', None), 'type', '') == 'cuda'
+
+
 class _HostRing(object):
     """Pinned host buffers for the FASTQ bytes on their way out: the device-to-host copy of
     a finished batch lands in page-locked memory (full PCIe rate, no staging copy by the runtime) and a writer thread
     hands it to the sink while the GPU works on the next batches.  A buffer returns to the ring when the writer is done
     with it; `depth` buffers bound the memory and apply back-pressure when the sink is slower than the GPU."""
 
-    def __init__(self, torch, pinned, depth=3):
-        import queue
-        import threading
+    def __init__(self, torch, pinned, sink, defer_errors=False, depth=3):
         self.torch, self.pinned = torch, pinned
+        # The buffers are allocated (and grown) on first use.  (Pinning them beside the first batch looked free and was not: 3 x 2.6 GB of
+        # hipHostMalloc against the clone threads' 40 GB arenas made every clone take 1.1 s instead of 0.05, profiles/r05b_cli_30x.json.)
         self.free = queue.Queue()
         for _ in range(depth):
-            self.free.put(None)                     # allocated (and grown) on first use
+            self.free.put(None)
         self.todo = queue.Queue()
         self.error = None
-        self.defer_errors = False                   # multi-rank runs: a failed sink is reported through the per-batch exchange, so that every rank stops at the same batch
-        self.sink = None
+        self.defer_errors = defer_errors            # multi-rank runs: a failed sink is reported through the per-batch exchange, so that every rank stops at the same batch
+        self.sink = sink
         self.sink_seconds = self.alloc_seconds = 0.0
         self.copy_stream = None                     # device -> pinned copies of the batches' bytes (write)
         self.thread = threading.Thread(target=self._run, daemon=True)
         self.thread.start()
-
-    def prealloc(self, nbytes):
-        """Page-lock the ring's buffers NOW, on a thread of their own, while the first device batch computes (pinning 3 x 2.5 GB
-        is ~1 s that the consumer thread spent at its first writes: profiles/r04_cli_30x.json, ring_alloc 0.95 s)."""
-        import threading
-        if not self.pinned or nbytes <= 0:
-            return
-        slots = []
-        while True:                                  # take the empty slots; whatever is in use already stays as it is
-            try:
-                slots.append(self.free.get_nowait())
-            except Exception:
-                break
-
-        def make():
-            for slot in slots:
-                if slot is None:
-                    try:
-                        slot = self.torch.empty(int(nbytes), dtype=self.torch.uint8, pin_memory=True)
-                    except Exception:                # not fatal: stage() allocates what it needs
-                        slot = None
-                self.free.put(slot)
-        threading.Thread(target=make, daemon=True).start()
 
     def _run(self):
         while True:
@@ -392,20 +439,18 @@ class _HostRing(object):
 
     def write(self, tensor):
         """Copy a uint8 tensor (device or host) into a ring buffer and queue it for the sink.  A device tensor is copied
-        ASYNCHRONOUSLY on the ring's own stream: the consumer thread goes on to the next batch (stop rule, refill of the pipeline)
-        while the bytes cross PCIe, and the writer thread waits for the copy, not the consumer -- on configs[4] the consumer spent
-        5.0 of the read loop's 9.1 s inside blocking copies (profiles/r04_cli_30x_hifi.json).  The source tensor travels with
-        the queue entry so that its memory is not reused before the copy has read it."""
+        ASYNCHRONOUSLY on the ring's own stream: the consumer thread goes on to the next batch (stop rule, refill of the pipeline) while the
+        bytes cross PCIe, and the writer thread waits for the copy, not the consumer (which spent 5.0 of configs[4]'s 9.1 s of read loop inside
+        blocking copies, profiles/r04_cli_30x_hifi.json).  The source tensor travels with the queue entry: its memory is not reused before."""
         n = int(tensor.numel())
         buf = self.stage(n)
         landed = None
         if n and self.pinned and tensor.is_cuda and not os.environ.get('BRX_SYNC_COPY_OUT'):
             torch = self.torch
             if self.copy_stream is None:
-                # (a high-priority stream for the copy was measured: BRX_COPY_PRIORITY=-1 made configs[4]'s read loop 9.8 s against 8.8 s at the
-                #  default priority, profiles/r05h; the copy itself runs at 57 GB/s on an idle GPU: tools/d2h_probe.py)
-                prio = int(os.environ.get('BRX_COPY_PRIORITY', '0'))
-                self.copy_stream = torch.cuda.Stream(device=tensor.device, priority=prio)
+                # (default priority: a high-priority stream, -1, made configs[4]'s read loop 9.8 s against 8.8 s, profiles/r05h;
+                #  the copy itself runs at 57 GB/s on an idle GPU: tools/d2h_probe.py)
+                self.copy_stream = torch.cuda.Stream(device=tensor.device)
             self.copy_stream.wait_stream(torch.cuda.current_stream(tensor.device))     # the tensor's producer has been waited for on the current stream
             with torch.cuda.stream(self.copy_stream):
                 buf[:n].copy_(tensor, non_blocking=True)
@@ -423,14 +468,12 @@ class _HostRing(object):
 
 
 class _ArenaPrefetch(object):
-    """The job's scratch arenas, allocated by threads of their own from the moment the first engine exists -- beside the model
-    tables, the genome's upload and the first batch -- instead of when the read loop asks for them.  On a freshly leased GPU a
-    40 GB arena is ~4 s of `hipMalloc` (the driver provisions and clears the memory: 21 s of thread time for the five clones of a
-    30x human job, profiles/r05_cli_30x.json); started 1.4 s before the loop, the engines are there 1.4 s earlier.  take() hands
-    out the next arena (waiting for its thread) or None."""
+    """The job's scratch arenas, allocated by threads of their own from the moment the first engine exists -- beside the model tables, the genome's
+    upload and the first batch -- instead of when the read loop asks for them.  On a freshly leased GPU a 40 GB arena is ~4 s of `hipMalloc` (the
+    driver provisions and clears the memory: 21 s of thread time for the five clones of a 30x human job, profiles/r05_cli_30x.json); started 1.4 s
+    before the loop, the engines are there 1.4 s earlier.  take() hands out the next arena (waiting for its thread) or None."""
 
     def __init__(self, torch, device, nbytes, count):
-        import threading
         self.nbytes, self.count = int(nbytes), int(count)
         self.slots = [None] * self.count
         self.errors = []
@@ -468,73 +511,59 @@ class _ArenaPrefetch(object):
     @staticmethod
     def for_job(engine, target_size, mean_length, error_rate, in_flight, world, truth_paf=False):
         """Arenas for the batches in flight of THIS job on THIS device, or None (not a GPU engine, a job of one small batch,
-        BRX_ARENA_PREFETCH=0).  How many: what the job will use and the free memory holds (_BatchPool.engines_that_fit's rule)."""
-        # Measured (profiles/r05i_arena_prefetch.json, r05k_*): the read loop then runs undisturbed -- 18.8-19.0 s for the 30x human job
-        # (20.9-23.7 without), 5.8-6.1 s = 15-16 Gbases/s for the configs[4] flavour (9.2 s).  What the allocations cost depends on what
-        # the GPU did before: right behind another process that gave 40+ GB back they are ~0.13 s per GB (the driver is still clearing),
-        # hold a lock the genome's upload waits for (0.2 -> 6.2 s) and the whole command takes what it took without this (27.2 s against
-        # 26.1-27.0 s); on a GPU that has been idle for 20 s they are nearly free and the command is 22.0 s against 23.4 s, 8.7 s
-        # against 11.6 s for configs[4].  Never slower, so on by default; BRX_ARENA_PREFETCH=0 is the round-4 behaviour.
-        if getattr(getattr(engine, 'device', None), 'type', '') != 'cuda' or os.environ.get('BRX_ARENA_PREFETCH', '1') in ('', '0'):
+        BRX_ARENA_PREFETCH=0).  How many: what the job will use and the free memory holds (engines_for_memory, no arena mapped yet)."""
+        # Measured (profiles/r05i_arena_prefetch.json, r05k_*; DESIGN.md has the figures): the read loop then runs undisturbed, 18.8-19.0 s for
+        # the 30x human job (20.9-23.7 without).  Right behind another process that gave 40+ GB back the allocations are ~0.13 s per GB and the
+        # command takes what it took without this; on an idle GPU they are nearly free.  Never slower, so on by default; BRX_ARENA_PREFETCH=0: off.
+        if not _on_gpu(engine) or os.environ.get('BRX_ARENA_PREFETCH', '1') in ('', '0'):
             return None
         from .engine import arena_estimate
-        torch = engine.torch
         first_batch = plan_batch(target_size, mean_length, world, DEFAULT_MAX_BATCH) // max(world, 1)
         if first_batch < 4096:
             return None                                  # a small job: one arena, sized by presize
         nbytes = engine.arena_bytes(first_batch, mean_length, error_rate) if hasattr(engine, 'arena_bytes') else arena_estimate(first_batch, mean_length, error_rate)
-        out_bytes = int(first_batch * (2.1 * mean_length + 400.0) * (1.0 + (PAF_SHARE if truth_paf else 0.0)))
+        out_bytes = expected_out_bytes(None, first_batch, mean_length, truth_paf)        # the engine's parameters are not set yet
         batches = -(-int(target_size) // max(int(first_batch * mean_length * max(world, 1)), 1))
-        n = max(1, min(int(in_flight), batches))
-        free, _ = torch.cuda.mem_get_info(engine.device)
-        reserve = int(float(os.environ.get('BRX_DRIVER_RESERVE_GB', '24')) * (1 << 30))
-        while n > 1 and n * nbytes + (2 * n + 2) * out_bytes + reserve > free:
-            n -= 1
-        return _ArenaPrefetch(torch, engine.device, nbytes, n)
+        free, _ = engine.torch.cuda.mem_get_info(engine.device)
+        n = engines_for_memory(free, max(1, min(int(in_flight), batches)), nbytes, 0, out_bytes, driver_reserve_bytes())
+        return _ArenaPrefetch(engine.torch, engine.device, nbytes, n)
+
+
+class _Done(object):
+    """A finished batch behind a future's interface: what a pool of one engine, which has no worker thread, hands back."""
+    def __init__(self, v): self.v = v
+    def result(self): return self.v
 
 
 class _BatchPool(object):
-    """`in_flight` engines (the given one + clones sharing its device tables), each driven by its own host thread on
-    its own HIP stream, so that several batches overlap on the GPU.
+    """`in_flight` engines (the given one + clones sharing its device tables), each driven by its own host thread on its own HIP stream, so that
+    several batches overlap on the GPU.
 
-    Batches are CONSUMED in index order (the stop rule), but they do not FINISH in index order: read lengths differ, and so do
-    batch times.  Round 2 released an engine only when its batch was consumed, so an engine that had finished batch k + 3
-    idled until batches k .. k + 2 were through -- every round of six batches took as long as its slowest member, and a 30x job
-    through this driver ran at 60-70 % of the rate bench.py measures on the same kernels.  Now the worker thread itself takes
-    a free engine when it starts a batch, copies the batch's FASTQ bytes device-to-device out of the engine's buffer when the
-    batch is done (2 GB at HBM speed: ~1 ms) and gives the engine back at once; `depth` = in_flight + 2 batches may be outstanding,
-    the surplus holding only their bytes."""
+    Batches are CONSUMED in index order (the stop rule), but they do not FINISH in index order: read lengths differ, and so do batch times.  An engine
+    released only when its batch is consumed idles behind the slowest of the batches before it (60-70 % of the rate bench.py measures on the same
+    kernels: DESIGN.md, "Through the CLI driver"), so the worker thread itself takes a free engine when it starts a batch, copies the batch's FASTQ
+    bytes device-to-device out of the engine's buffer when the batch is done (2 GB at HBM speed: ~1 ms) and gives the engine back at once; `depth` =
+    in_flight + 2 batches may be outstanding, the surplus holding only their bytes."""
 
     def __init__(self, engine, in_flight, arenas=None, device_gzip=False, truth_paf=False):
-        import concurrent.futures
-        import queue
         self.arenas = arenas
         self.truth_paf = bool(truth_paf)                 # --truth-paf: every batch's truth alignments, made by its worker beside its FASTQ
-        # --gzip-device: the worker of a batch that the stop rule cannot cut (submit(..., pack=True): the job still needs several
-        # batches' worth of bases behind it) packs ITS batch on ITS engine's stream as soon as the batch is done and hands over
-        # the gzip members instead of the text; the consumer packs only the job's last batches itself.  Round 5 packed every batch
-        # on the consumer thread: 9.3 s for the 185 GB of text of the configs[4] job, which bound that flavour (10.4 s of read
-        # loop against 6.0 s; VERDICT r5).
+        # --gzip-device: the worker of a batch that the stop rule cannot cut (submit(..., pack=True)) packs ITS batch on ITS engine's stream and hands
+        # over the gzip members; the consumer packs only the job's last batches (every batch there: 10.4 s of configs[4]'s read loop against 6.0 s)
         self.device_gzip = bool(device_gzip)
-        self.engines = [engine]
-        self.streams = [None]
         torch = getattr(engine, 'torch', None)           # absent on the tests' CPU checker engines
-        self.on_gpu = torch is not None and getattr(engine, 'device', None) is not None and engine.device.type == 'cuda'
-        if in_flight > 1 and hasattr(engine, 'clone'):
-            self.streams = [torch.cuda.Stream(device=engine.device) if self.on_gpu else None for _ in range(in_flight)]
-            self.engines += [None] * (in_flight - 1)
-        elif self.on_gpu:
-            self.streams = [torch.cuda.Stream(device=engine.device)]
+        self.on_gpu = torch is not None and _on_gpu(engine)
+        n = in_flight if in_flight > 1 and hasattr(engine, 'clone') else 1
+        self.engines = [engine] + [None] * (n - 1)
+        self.streams = [torch.cuda.Stream(device=engine.device) if self.on_gpu else None for _ in range(n)]
         self.free = queue.Queue()
         self.free.put(0)                                 # engine 0 exists already: it takes the first batch
         self.create_seconds = 0.0
         self.create_errors = []                          # clones that could not be made: the job runs on fewer engines
-        import threading
         self.lock = threading.Lock()                     # the counters below are updated by several worker threads
-        # Mapping a clone's 40 GB arena takes ~0.6-1.2 s per engine whoever does it and whenever (the driver clears the memory:
-        # 14-29 ms per GB measured, also for ONE 200 GB allocation on an idle device -- 5.9 s), so the clones are made by their own
-        # threads while engine 0 already computes: a job's first seconds run on fewer engines instead of on none.  Clone i is
-        # started when the job submits its (i + 1)-th batch: a one-batch job (a bacterial genome at 100x) maps no clone at all.
+        # Mapping a clone's 40 GB arena takes ~0.6-1.2 s per engine whoever does it and whenever (the driver clears the memory: 14-29 ms per
+        # GB, also for ONE 200 GB allocation on an idle device), so the clones are made by their own threads while engine 0 already computes.
+        # Clone i is started when the job submits its (i + 1)-th batch: a one-batch job (a bacterial genome at 100x) maps no clone at all.
         def make(i):                                     # a clone maps tens of GB of scratch: its own thread, beside the first batches
             t0 = time.perf_counter()
             try:
@@ -542,14 +571,13 @@ class _BatchPool(object):
                     torch.cuda.set_device(self.engines[0].device)
                 spare = self.arenas.take() if self.arenas is not None else None       # allocated since the first engine exists, or None
                 self.engines[i] = self.engines[0].clone(scratch_tensor=spare) if spare is not None else self.engines[0].clone()
+                self.free.put(i)
             except BaseException as ex:                  # this slot never joins the queue; engine 0 and the other clones carry on
                 with self.lock:
                     self.create_errors.append(ex)
+            finally:
+                with self.lock:
                     self.create_seconds += time.perf_counter() - t0
-                return
-            with self.lock:
-                self.create_seconds += time.perf_counter() - t0
-            self.free.put(i)
         self.makers = [threading.Thread(target=make, args=(i,), daemon=True) for i in range(1, len(self.engines))]
         self.started = 0                                 # makers started so far
         self.submitted = 0
@@ -563,31 +591,20 @@ class _BatchPool(object):
 
     @staticmethod
     def engines_that_fit(torch, engine, in_flight, out_bytes):
-        """How many engines the device's FREE memory holds: every clone maps an arena as large as the first engine's, every engine
-        owns an output buffer, and in_flight + 2 copies of a batch's bytes may wait for the consumer.  A reserve stays free for what
-        the runtime allocates on its own: the private segments of the planning kernels (1.6 KB per lane, per hardware queue: ~0.9 GB
-        each over the ~20 queues of a six-engine job), the gzip stage, other ranks' records on rank 0.  A job that asks for more
-        engines than fit runs on fewer (a 96-batch job of six 65536-read engines with 40 GB arenas died with
-        HSA_STATUS_ERROR_OUT_OF_RESOURCES at the edge of the 288 GB, where no allocation of ours failed)."""
+        """How many engines the device's FREE memory holds (engines_for_memory): every clone maps an arena as large as the first engine's."""
         torch.cuda.empty_cache()
-        free, total = torch.cuda.mem_get_info(engine.device)
-        reserve = int(float(os.environ.get('BRX_DRIVER_RESERVE_GB', '24')) * (1 << 30))
+        free, _ = torch.cuda.mem_get_info(engine.device)
         scratch = engine.scratch_bytes() if hasattr(engine, 'scratch_bytes') else 0
-        n = in_flight
-        while n > 1 and (n - 1) * scratch + (2 * n + 2) * int(out_bytes) + reserve > free:
-            n -= 1
-        return n
+        return engines_for_memory(free, in_flight, scratch, 1, int(out_bytes), driver_reserve_bytes())       # the first engine's arena is mapped already
 
     COPY_STEP = 1 << 28
 
     @classmethod
     def _copy_of(cls, torch, out):
-        """The batch's bytes out of the engine's buffer, in a block whose CAPACITY is a multiple of 256 MB.  A plain clone() asks
-        torch's caching allocator for the batch's exact size -- 2.05-2.10 GB, a different one every time -- and a cached block that is
-        a few MB short serves nobody: it stays cached (per stream) and a new one is mapped.  Over the 94 batches of the 30x job
-        the cache crept through the 24 GB this driver leaves to the runtime, and a queue that needed its private segment then
-        died with HSA_STATUS_ERROR_OUT_OF_RESOURCES at 88 % of the job (`Available Free mem : 0 MB`; no allocation of ours had
-        failed).  With the capacity in steps every freed block fits the next batch."""
+        """The batch's bytes out of the engine's buffer, in a block whose CAPACITY is a multiple of 256 MB.  A plain clone() asks torch's caching
+        allocator for the batch's exact size -- 2.05-2.10 GB, never the same twice -- and a cached block a few MB short serves nobody: it stays
+        cached and a new one is mapped, until over the 94 batches of the 30x job the cache had crept through the driver's reserve and a queue's
+        private segment failed with HSA_STATUS_ERROR_OUT_OF_RESOURCES.  In steps, every freed block fits the next batch."""
         n = int(out.numel())
         if n <= cls.COPY_STEP // 16:
             return out.clone()
@@ -601,51 +618,48 @@ class _BatchPool(object):
         while self.started < min(self.submitted - 1, len(self.makers)):      # the k-th batch in the pipeline is what clone k - 1 is for
             self.makers[self.started].start()
             self.started += 1
-
-        def job():
-            import torch
-            t_q = time.perf_counter()
-            i = self.free.get()
-            t_job = time.perf_counter()
-            with self.lock:
-                self.wait_engine_seconds += t_job - t_q
-            try:
-                stream = self.streams[i]
-                eng = self.engines[i]
-                if n_mine == 0:
-                    return torch.zeros(0, dtype=torch.uint8), np.zeros(0, dtype=eng.stats_dtype), None, None
-                if not self.on_gpu:
-                    out, stats = eng.simulate_batch(seed, first, n_mine, allow_nofrag=True)
-                    paf = eng.emit_paf_device(n_mine) if self.truth_paf else None
-                    return torch.from_numpy(np.ascontiguousarray(out).copy()), stats.copy(), None, paf
-                torch.cuda.set_device(eng.device)
-                with torch.cuda.stream(stream):
-                    out, stats = eng.simulate_batch_device(seed, first, n_mine, allow_nofrag=True)
-                    # the truth alignments read what the batch left in the engine's arena: same job, same stream, before the engine is free
-                    paf = eng.emit_paf_device(n_mine) if self.truth_paf else None
-                    stats = stats.copy()
-                    packed = None
-                    if pack and self.device_gzip and len(stats) and hasattr(eng, 'gzip_device'):
-                        from .output import fastq_blocks
-                        live = np.flatnonzero(stats['rec_len'] > 0)
-                        if len(live) and not (stats['status'] & (RS_NOFRAG | BAD_STATUS)).any():
-                            nbytes = int(stats['rec_off'][live[-1]] + stats['rec_len'][live[-1]])
-                            blocks = fastq_blocks(stats['rec_off'], stats['rec_len'], stats['seq_len'], nbytes)
-                            packed = (nbytes, eng.gzip_device(out[:nbytes], blocks))      # a new tensor, made on this batch's stream
-                    out = self._copy_of(torch, out) if packed is None else None   # the engine's buffer is free again; the copy runs on this batch's stream ...
-                    stream.synchronize()                     # ... and is complete before the engine is handed to the next batch
-                    return out, stats, packed, paf
-            finally:
-                with self.lock:
-                    self.job_seconds += time.perf_counter() - t_job
-                    self.job_count += 1
-                self.free.put(i)
         if self.pool is None:
-            class _Done(object):
-                def __init__(self, v): self.v = v
-                def result(self): return self.v
-            return _Done(job())
-        return self.pool.submit(job)
+            return _Done(self._work(seed, first, n_mine, pack))
+        return self.pool.submit(self._work, seed, first, n_mine, pack)
+
+    def _work(self, seed, first, n_mine, pack):
+        """One batch on the next free engine, on a worker thread: (FASTQ bytes, stats, (text bytes, gzip members) or None, PAF or None)."""
+        import torch
+        t_q = time.perf_counter()
+        i = self.free.get()
+        t_job = time.perf_counter()
+        with self.lock:
+            self.wait_engine_seconds += t_job - t_q
+        try:
+            stream, eng = self.streams[i], self.engines[i]
+            if n_mine == 0:
+                return torch.zeros(0, dtype=torch.uint8), np.zeros(0, dtype=eng.stats_dtype), None, None
+            if not self.on_gpu:
+                out, stats = eng.simulate_batch(seed, first, n_mine, allow_nofrag=True)
+                paf = eng.emit_paf_device(n_mine) if self.truth_paf else None
+                return torch.from_numpy(np.ascontiguousarray(out).copy()), stats.copy(), None, paf
+            torch.cuda.set_device(eng.device)
+            with torch.cuda.stream(stream):
+                out, stats = eng.simulate_batch_device(seed, first, n_mine, allow_nofrag=True)
+                # the truth alignments read what the batch left in the engine's arena: same job, same stream, before the engine is free
+                paf = eng.emit_paf_device(n_mine) if self.truth_paf else None
+                stats = stats.copy()
+                packed = None
+                if pack and self.device_gzip and len(stats) and hasattr(eng, 'gzip_device'):
+                    from .output import fastq_blocks
+                    live = np.flatnonzero(stats['rec_len'] > 0)
+                    if len(live) and not (stats['status'] & (RS_NOFRAG | BAD_STATUS)).any():
+                        nbytes = int(stats['rec_off'][live[-1]] + stats['rec_len'][live[-1]])
+                        blocks = fastq_blocks(stats['rec_off'], stats['rec_len'], stats['seq_len'], nbytes)
+                        packed = (nbytes, eng.gzip_device(out[:nbytes], blocks))      # a new tensor, made on this batch's stream
+                out = self._copy_of(torch, out) if packed is None else None   # the engine's buffer is free again; the copy runs on this batch's stream ...
+                stream.synchronize()                     # ... and is complete before the engine is handed to the next batch
+                return out, stats, packed, paf
+        finally:
+            with self.lock:
+                self.job_seconds += time.perf_counter() - t_job
+                self.job_count += 1
+            self.free.put(i)
 
     def close(self):
         for th in self.makers[:self.started]:            # clones no batch asked for were never started
@@ -687,204 +701,187 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
     A sink that fails on one rank of a multi-rank run (a full disk, a closed pipe) is reported in the same exchange -- one
     word per rank -- so that every rank leaves the loop at the same batch instead of waiting in a collective.
     """
-    import collections
-    import torch
-    shard = shard or Shard()
-    max_batch = max_batch or DEFAULT_MAX_BATCH
-    count = total = 0
-    next_read = 0
-    expected_mean = float(mean_length)
-    if shard.rank == 0:
-        print_progress(count, total, target_size, output)
-    timing = run_batches.last_timing = collections.Counter()     # seconds of the consumer thread per activity (bench.py --d2h)
-    t0 = time.perf_counter()
-    t_job = t0
-    first_arena = None
-    if hasattr(engine, 'presize'):               # the arena of the first engine (the clones copy its size) for the batches this job will issue
-        first_batch = plan_batch(target_size, expected_mean, shard.world, max_batch) // shard.world
-        first_arena = arenas.take() if arenas is not None else None
-        if first_arena is not None:              # allocated beside the start-up (simulate._ArenaPrefetch)
-            engine.adopt_scratch(first_arena)
-        elif expected_error is None:
-            engine.presize(first_batch, expected_mean)
-        else:                                    # the job's identity law: arenas for Q30 reads are half those of 95 % reads
-            engine.presize(first_batch, expected_mean, expected_error)
-        out_bytes = int(first_batch * (engine.expected_record_bytes() if hasattr(engine, 'expected_record_bytes') else 2.1 * expected_mean + 400.0))
-        if truth_paf:                            # every batch in flight also holds its PAF text on the device
-            out_bytes = int(out_bytes * (1.0 + PAF_SHARE))
-    else:
-        out_bytes = 0
-    asked = fit = max(1, int(in_flight))
-    if arenas is not None and first_arena is not None:
-        fit = min(fit, arenas.count)             # decided when the arenas were requested, by the same rule, from the memory that was free then
-    elif fit > 1 and hasattr(engine, 'scratch_bytes') and getattr(getattr(engine, 'device', None), 'type', '') == 'cuda':
-        fit = _BatchPool.engines_that_fit(engine.torch, engine, fit, out_bytes)
-    if shard.world > 1:                          # the issue schedule depends on the depth of the pipeline: the same on every rank
-        fit = min(int(x[0]) for x in shard.gather_words(np.array([fit], dtype=np.uint32), [1] * shard.world))
-    if fit < asked and shard.rank == 0:
-        print(f'  {fit} of the {asked} batches in flight asked for fit into the free device memory', file=output)
-    pool = _BatchPool(engine, fit, arenas, device_gzip=device_gzip, truth_paf=truth_paf)
-    timing['create_engines'] = time.perf_counter() - t0
-    ring = None
-    if local_write is not None or shard.rank == 0:
-        ring = _HostRing(torch, pinned=pool.on_gpu)
-        ring.sink = local_write if local_write is not None else write
-        ring.defer_errors = shard.world > 1
-        # (Pinning the ring's buffers on a thread of their own beside the first batch looked free and was not: 3 x 2.6 GB of
-        #  hipHostMalloc ran against the clone threads' 40 GB arenas and every clone took 1.1 s instead of 0.05 -- 5.6 s of
-        #  wait_for_engine, profiles/r05b_cli_30x.json.  BRX_RING_PREALLOC=1 keeps the experiment reachable.)
-        if pool.on_gpu and out_bytes and os.environ.get('BRX_RING_PREALLOC') and target_size > 3 * max_batch * expected_mean:
-            ring.prealloc(int(1.25 * out_bytes))
-    paf_ring = None
-    if truth_paf and paf_write is not None:
-        paf_ring = _HostRing(torch, pinned=pool.on_gpu)      # the PAF text leaves through its own ring and writer thread
-        paf_ring.sink = paf_write
-        paf_ring.defer_errors = shard.world > 1
-    sink_failed_on = None
-
-    def staging(nbytes):
-        """Where rank 0 receives another rank's records (device memory under RCCL): a tensor of ITS OWN per receive.  The ring
-        copies device tensors to the host asynchronously on its copy stream and keeps the tensor with the queue entry until the
-        copy has landed; one reused staging buffer would be overwritten by the next rank's `recv` (ordered behind the current
-        stream only) while that copy still reads it.  The caching allocator makes this as cheap as the reuse was."""
-        return torch.empty(int(nbytes), dtype=torch.uint8, device=shard._device())
-
-    gz_engine = None
-    if device_gzip:
-        if not hasattr(engine, 'gzip_device'):
-            sys.exit('Error: --gzip-device needs the GPU engine')
-        from .output import fastq_blocks
-        gz_engine = engine.clone(1 << 20) if hasattr(engine, 'clone') else engine      # its own context: the others are busy on their threads
-    pending = collections.deque()          # (None, future, first_of_super_batch, n_super, first, n_mine)
-    fatal = bad_read = None
-
-    def fill():
-        """Keep the pipeline full: what is outstanding is assumed to deliver its expected number of bases.  Called at
-        points that depend only on consumed totals, so every rank issues the same batches."""
-        nonlocal next_read
-        while len(pending) < len(pool):
-            outstanding = sum(p[3] for p in pending) * expected_mean
-            remaining = target_size - total - outstanding
-            if remaining <= 0 and pending:
-                break
-            n_super = plan_batch(max(remaining, 1), expected_mean, shard.world, max_batch)
-            first, n_mine = shard.slice_of(next_read, n_super)
-            # --gzip-device: a batch with at least three batches' worth of bases still to come behind it is kept whole
-            fut = pool.submit(seed, first, n_mine, pack=device_gzip and remaining > 4.0 * n_super * expected_mean)
-            pending.append((None, fut, next_read, n_super, first, n_mine))
-            next_read += n_super
-
+    run = _Run(engine, seed, target_size, mean_length, write, output, shard or Shard(), max_batch or DEFAULT_MAX_BATCH, in_flight,
+               device_gzip, local_write, local_parts, expected_error, arenas, truth_paf, paf_write)
+    run_batches.last_timing = run.timing
+    run.size_pipeline()
+    run.open_rings()
     try:
-        while total < target_size:
-            fill()
-            _, fut, base, n_super, first, n_mine = pending.popleft()
-            t0 = time.perf_counter()
-            res = fut.result()
-            out, stats, prepacked, paf = res
-            timing['wait_for_batch'] += time.perf_counter() - t0
-            timing['batches'] += 1
-            # ---- the 4 B/read exchange: length (0 for skipped reads) | NOFRAG << 31 | BAD << 30 ----
-            words = (stats['seq_len'].astype(np.uint32) * (stats['rec_len'] > 0)).astype(np.uint32)
-            assert not len(words) or int(words.max()) < FLAG_BAD
-            words |= np.where(stats['status'] & RS_NOFRAG, FLAG_NOFRAG, 0).astype(np.uint32)
-            words |= np.where(stats['status'] & BAD_STATUS, FLAG_BAD, 0).astype(np.uint32)
-            per_rank = [Shard(r, shard.world).slice_of(base, n_super)[1] for r in range(shard.world)]
-            if shard.world > 1:                     # one more word per rank: "my sink has failed"
-                failed_here = any(x is not None and x.error is not None for x in (ring, paf_ring))     # the FASTQ's sink or the PAF's
-                mine = np.append(words, np.uint32(1 if failed_here else 0))
-                parts = shard.gather_words(mine, [c + 1 for c in per_rank])
-                failed = [r for r, part in enumerate(parts) if part[-1]]
-                if failed:
-                    sink_failed_on = failed[0]
-                    break
-                allw = np.concatenate([part[:-1] for part in parts])
-            else:
-                allw = words
-            lens = (allw & (FLAG_BAD - 1)).astype(np.int64)
-            cut = cut_point(lens, total, target_size)
-            wrong = np.flatnonzero(allw & (FLAG_NOFRAG | FLAG_BAD))
-            stop_at = None
-            if len(wrong) and (cut is None or wrong[0] < cut):
-                stop_at = int(wrong[0])
-                if allw[stop_at] & FLAG_NOFRAG:
-                    fatal = True
-                else:
-                    bad_read = base + stop_at
-            last = stop_at - 1 if stop_at is not None else (cut if cut is not None else n_super - 1)
-            # bytes of my reads with global batch position <= last
-            my_lo = first - base
-            keep = int(np.clip(last - my_lo + 1, 0, n_mine))
-            my_bytes = int(stats['rec_off'][keep - 1] + stats['rec_len'][keep - 1]) if keep else 0
-            packed = False
-            if prepacked is not None and my_bytes == prepacked[0]:          # the whole batch is kept: its worker has packed it already
-                out = prepacked[1]
-                my_bytes = int(out.numel())
-                packed = True
-                timing['batches_packed_by_their_worker'] += 1
-            elif prepacked is not None:
-                # the stop rule cut a batch that was packed ahead (reads far longer than the job expected): unpack it on the host, once
-                import gzip as _gzip
-                text = _gzip.decompress(bytes(prepacked[1].cpu().numpy()))
-                out = torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).to(prepacked[1].device)
-            if gz_engine is not None and my_bytes and not packed:
-                t0 = time.perf_counter()
-                blocks = fastq_blocks(stats['rec_off'][:keep], stats['rec_len'][:keep], stats['seq_len'][:keep], my_bytes)
-                out = gz_engine.gzip_device(out[:my_bytes], blocks)       # a new tensor: the engine's buffer is free again
-                my_bytes = int(out.numel())
-                packed = True
-                timing['device_gzip'] += time.perf_counter() - t0
-            sizes = [my_bytes]
-            if shard.world > 1 and local_write is None:
-                sizes = [int(x[0]) for x in shard.gather_words(np.array([my_bytes], dtype=np.uint32), [1] * shard.world)]
-                assert my_bytes < 2 ** 32
-            if pool.on_gpu and my_bytes and not packed:
-                out = out[:my_bytes]                # `out` is this batch's own copy (made by its worker): nothing to wait for
-            used = lens[:last + 1]
-            count += int((used > 0).sum())
-            total += int(used.sum())
-            stop = fatal or bad_read is not None
-            if count and not stop:
-                expected_mean = max(total / count, 1.0)
-            if not stop and total < target_size:
-                fill()                              # the freed engine starts its next batch while this one's bytes leave
-            t0 = time.perf_counter()
-            if local_write is not None:             # every rank: its own bytes through its own ring to its own file
-                if my_bytes:
-                    ring.write(out[:my_bytes])
-                if local_parts is not None:
-                    local_parts(my_bytes)
-            else:
-                for _, part in shard.collect_bytes(out, sizes, staging):
-                    ring.write(part)                # rank 0: through pinned memory to the writer thread
-            if truth_paf:                           # the records of the same reads, the same way
-                paf_bytes = int(paf[1][keep]) if paf is not None else 0
-                if local_write is not None or shard.world == 1:
-                    if paf_bytes and paf_ring is not None:
-                        paf_ring.write(paf[0][:paf_bytes])
-                else:
-                    paf_sizes = [int(x[0]) for x in shard.gather_words(np.array([paf_bytes], dtype=np.uint32), [1] * shard.world)]
-                    assert paf_bytes < 2 ** 32
-                    for _, part in shard.collect_bytes(paf[0] if paf is not None else None, paf_sizes, staging):
-                        paf_ring.write(part)
-            timing['copy_out'] += time.perf_counter() - t0
-            if shard.rank == 0:
-                print_progress(count, total, target_size, output)
-            if stop:
+        while run.total < target_size:
+            run.fill()
+            if not run.consume(run.pending.popleft()):
                 break
     finally:
-        for _, fut, *_ in pending:          # speculative batches past the stopping read
-            try:
-                fut.result()
-            except Exception:
-                pass
-        if getattr(getattr(engine, 'device', None), 'type', '') == 'cuda':       # what the device looked like when the last batch was through (BRX_DRIVER_TIMING)
-            try:
-                free_b, _total_b = torch.cuda.mem_get_info(engine.device)
+        run.close(unwinding=sys.exc_info()[0] is not None)
+    if run.shard.rank == 0:
+        print('\n', file=output)
+    run.raise_outcome()
+    return run.count, run.total
+
+
+class _Run(object):
+    """One call of run_batches: its arguments, the pipeline and the consumed totals as attributes, its steps as methods.  Every collective
+    (Shard.gather_words, collect_bytes) and every pool.submit comes at a point that depends only on consumed totals: the ranks stay in step."""
+
+    def __init__(self, engine, seed, target_size, mean_length, write, output, shard, max_batch, in_flight, device_gzip,
+                 local_write, local_parts, expected_error, arenas, truth_paf, paf_write):
+        import torch
+        self.torch = torch
+        self.engine, self.seed, self.target_size, self.write, self.output, self.shard = engine, seed, target_size, write, output, shard
+        self.max_batch, self.in_flight, self.device_gzip, self.expected_error, self.arenas = max_batch, in_flight, device_gzip, expected_error, arenas
+        self.local_write, self.local_parts, self.truth_paf, self.paf_write = local_write, local_parts, truth_paf, paf_write
+        self.count = self.total = self.next_read = 0
+        self.expected_mean = float(mean_length)
+        self.pending = collections.deque()          # _Pending, in index order
+        self.fatal, self.bad_read, self.sink_failed_on = False, None, None
+        self.pool = self.ring = self.paf_ring = self.gz_engine = None
+        if shard.rank == 0:
+            print_progress(0, 0, target_size, output)
+        self.timing = collections.Counter()         # seconds of the consumer thread per activity (bench.py --d2h)
+        self.t_job = time.perf_counter()
+
+    def size_pipeline(self):
+        """The first engine's arena (the clones copy its size) for the batches this job will issue; as many engines as fit on every rank."""
+        engine, shard, arenas = self.engine, self.shard, self.arenas
+        first_arena, out_bytes = None, 0
+        if hasattr(engine, 'presize'):
+            first_batch = plan_batch(self.target_size, self.expected_mean, shard.world, self.max_batch) // shard.world
+            first_arena = arenas.take() if arenas is not None else None
+            if first_arena is not None:              # allocated beside the start-up (_ArenaPrefetch)
+                engine.adopt_scratch(first_arena)
+            else:                                    # by the job's identity law, if given: arenas for Q30 reads are half those of 95 % reads
+                engine.presize(first_batch, self.expected_mean, self.expected_error)
+            out_bytes = expected_out_bytes(engine, first_batch, self.expected_mean, self.truth_paf)
+        asked = fit = max(1, int(self.in_flight))
+        if first_arena is not None:
+            fit = min(fit, arenas.count)             # decided when the arenas were requested, by the same rule, from the memory that was free then
+        elif fit > 1 and hasattr(engine, 'scratch_bytes') and _on_gpu(engine):
+            fit = _BatchPool.engines_that_fit(engine.torch, engine, fit, out_bytes)
+        if shard.world > 1:                          # the issue schedule depends on the depth of the pipeline: the same on every rank
+            fit = min(shard.gather_word(fit))
+        if fit < asked and shard.rank == 0:
+            print(f'  {fit} of the {asked} batches in flight asked for fit into the free device memory', file=self.output)
+        self.pool = _BatchPool(engine, fit, arenas, device_gzip=self.device_gzip, truth_paf=self.truth_paf)
+        self.timing['create_engines'] = time.perf_counter() - self.t_job
+
+    def open_rings(self):
+        """A ring for the FASTQ bytes (rank 0, or every rank with local_write), one of its own for the PAF text, the consumer's gzip engine."""
+        pinned, defer = self.pool.on_gpu, self.shard.world > 1
+        if self.local_write is not None or self.shard.rank == 0:
+            self.ring = _HostRing(self.torch, pinned, self.local_write if self.local_write is not None else self.write, defer)
+        if self.truth_paf and self.paf_write is not None:
+            self.paf_ring = _HostRing(self.torch, pinned, self.paf_write, defer)
+        if self.device_gzip:
+            if not hasattr(self.engine, 'gzip_device'):
+                sys.exit('Error: --gzip-device needs the GPU engine')
+            self.gz_engine = self.engine.clone(1 << 20) if hasattr(self.engine, 'clone') else self.engine      # its own context: the others are busy
+
+    def staging(self, nbytes):
+        """Where rank 0 receives another rank's records (device memory under RCCL): a tensor of ITS OWN per receive.  The ring copies device tensors
+        asynchronously and keeps them until the copy has landed; one reused buffer would be overwritten by the next rank's `recv` meanwhile."""
+        return self.torch.empty(int(nbytes), dtype=self.torch.uint8, device=self.shard._device())
+
+    def fill(self):
+        """Keep the pipeline full: what is outstanding is assumed to deliver its expected number of bases.  Called at
+        points that depend only on consumed totals, so every rank issues the same batches."""
+        while len(self.pending) < len(self.pool):
+            outstanding = sum(p.n_super for p in self.pending) * self.expected_mean
+            remaining = self.target_size - self.total - outstanding
+            if remaining <= 0 and self.pending:
+                break
+            n_super = plan_batch(max(remaining, 1), self.expected_mean, self.shard.world, self.max_batch)
+            first, n_mine = self.shard.slice_of(self.next_read, n_super)
+            # --gzip-device: a batch with at least three batches' worth of bases still to come behind it is kept whole
+            pack = self.device_gzip and remaining > 4.0 * n_super * self.expected_mean
+            self.pending.append(_Pending(self.pool.submit(self.seed, first, n_mine, pack=pack), self.next_read, n_super, first, n_mine))
+            self.next_read += n_super
+
+    def consume(self, batch):
+        """The next super-batch in index order: wait, exchange, decide, pack, account, refill, ship.  False: the loop ends here."""
+        timing, shard, t0 = self.timing, self.shard, time.perf_counter()
+        out, stats, prepacked, paf = batch.future.result()
+        timing['wait_for_batch'] += time.perf_counter() - t0
+        timing['batches'] += 1
+        allw = exchange_words(stats)
+        if shard.world > 1:                         # every rank's words in read order, and one more of each rank: "my sink has failed" (FASTQ's or PAF's)
+            per_rank = [Shard(r, shard.world).slice_of(batch.base, batch.n_super)[1] for r in range(shard.world)]
+            failed_here = any(x is not None and x.error is not None for x in (self.ring, self.paf_ring))
+            parts = shard.gather_words(np.append(allw, np.uint32(1 if failed_here else 0)), [c + 1 for c in per_rank])
+            failed = [r for r, part in enumerate(parts) if part[-1]]
+            if failed:                              # every rank leaves here, at the same batch
+                self.sink_failed_on = failed[0]
+                return False
+            allw = np.concatenate([part[:-1] for part in parts])
+        last, self.fatal, self.bad_read = stop_decision(allw, batch.base, self.total, self.target_size)
+        keep, my_bytes = kept_bytes(stats, batch.first, batch.base, last, batch.n_mine)
+        out, my_bytes = self.pack(out, stats, prepacked, keep, my_bytes)
+        local = self.local_write is not None       # every rank: its own bytes through its own ring to its own file
+        sizes = None if local else [my_bytes]
+        if shard.world > 1 and not local:
+            sizes = shard.gather_word(my_bytes)
+            assert my_bytes < 2 ** 32
+        used = (allw & (FLAG_BAD - 1)).astype(np.int64)[:last + 1]
+        self.count += int((used > 0).sum())
+        self.total += int(used.sum())
+        stop = self.fatal or self.bad_read is not None
+        if self.count and not stop:
+            self.expected_mean = max(self.total / self.count, 1.0)
+        if not stop and self.total < self.target_size:
+            self.fill()                             # the freed engine starts its next batch while this one's bytes leave
+        t0 = time.perf_counter()
+        self.ship(self.ring, out, my_bytes, sizes)
+        if local and self.local_parts is not None:
+            self.local_parts(my_bytes)
+        if self.truth_paf:                          # the records of the same reads, the same way
+            paf_bytes, paf_sizes = int(paf[1][keep]) if paf is not None else 0, None
+            if shard.world > 1 and not local:
+                paf_sizes = shard.gather_word(paf_bytes)
+                assert paf_bytes < 2 ** 32
+            self.ship(self.paf_ring, paf[0] if paf is not None else None, paf_bytes, paf_sizes)
+        timing['copy_out'] += time.perf_counter() - t0
+        if shard.rank == 0:
+            print_progress(self.count, self.total, self.target_size, self.output)
+        return not stop
+
+    def pack(self, out, stats, prepacked, keep, my_bytes):
+        """(what leaves, its bytes) for this rank's first `keep` reads, `my_bytes` of text.  --gzip-device: a batch its worker packed
+        whole leaves as it is; one the stop rule cut after all is unpacked and, like every batch not packed ahead, packed here."""
+        if prepacked is not None and my_bytes == prepacked[0]:
+            self.timing['batches_packed_by_their_worker'] += 1
+            return prepacked[1], int(prepacked[1].numel())
+        if prepacked is not None:      # reads far longer than the job expected: unpack on the host, once
+            text = gzip.decompress(bytes(prepacked[1].cpu().numpy()))
+            out = self.torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).to(prepacked[1].device)
+        if self.gz_engine is not None and my_bytes:
+            from .output import fastq_blocks
+            t0 = time.perf_counter()
+            blocks = fastq_blocks(stats['rec_off'][:keep], stats['rec_len'][:keep], stats['seq_len'][:keep], my_bytes)
+            out = self.gz_engine.gzip_device(out[:my_bytes], blocks)       # a new tensor: the engine's buffer is free again
+            my_bytes = int(out.numel())
+            self.timing['device_gzip'] += time.perf_counter() - t0
+        return out, my_bytes
+
+    def ship(self, ring, data, nbytes, sizes):
+        """`nbytes` of `data` into this rank's own `ring` (sizes None), or every rank's `sizes` bytes point to point into rank 0's."""
+        if sizes is None:
+            if nbytes and ring is not None:
+                ring.write(data[:nbytes])
+        else:
+            for _, part in self.shard.collect_bytes(data, sizes, self.staging):
+                ring.write(part)                    # rank 0: through pinned memory to the writer thread
+
+    def close(self, unwinding):
+        """Wait for what is in flight, close the engines, drain the rings.  `unwinding`: an exception propagates, which a sink's must not mask."""
+        torch, timing, pool, arenas = self.torch, self.timing, self.pool, self.arenas
+        for p in self.pending:              # speculative batches past the stopping read
+            with contextlib.suppress(Exception):
+                p.future.result()
+        if _on_gpu(self.engine):            # what the device looked like when the last batch was through (BRX_DRIVER_TIMING)
+            with contextlib.suppress(Exception):
+                free_b, _total_b = torch.cuda.mem_get_info(self.engine.device)
                 timing['device_free_gb_at_end'] = free_b / float(1 << 30)
-                timing['torch_reserved_gb_at_end'] = torch.cuda.memory_reserved(engine.device) / float(1 << 30)
-                timing['torch_allocated_gb_at_end'] = torch.cuda.memory_allocated(engine.device) / float(1 << 30)
-            except Exception:
-                pass
+                timing['torch_reserved_gb_at_end'] = torch.cuda.memory_reserved(self.engine.device) / float(1 << 30)
+                timing['torch_allocated_gb_at_end'] = torch.cuda.memory_allocated(self.engine.device) / float(1 << 30)
         t0 = time.perf_counter()
         pool.close()
         if arenas is not None:                  # arenas no clone asked for (a job that stopped early, ranks that agreed on fewer engines)
@@ -892,50 +889,48 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
             timing['arena_prefetch_thread_seconds'] = arenas.seconds
             if arenas.errors:                   # a prefetch that failed left its clone to allocate by itself: say so (it may be what ran out of memory later)
                 timing['arena_prefetch_failures'] = len(arenas.errors)
-                if shard.rank == 0:
+                if self.shard.rank == 0:
                     print(f'  {len(arenas.errors)} of the {arenas.count} scratch arenas could not be allocated ahead '
-                          f'({type(arenas.errors[0]).__name__}: {arenas.errors[0]})', file=output)
-        if gz_engine is not None and gz_engine is not engine:
-            gz_engine.close()
+                          f'({type(arenas.errors[0]).__name__}: {arenas.errors[0]})', file=self.output)
+        if self.gz_engine is not None and self.gz_engine is not self.engine:
+            self.gz_engine.close()
         timing['close_engines'] = time.perf_counter() - t0
         t0 = time.perf_counter()
-        if ring is not None:
-            # a sink error must not mask the exception that is already propagating; in a multi-rank run it is reported below
-            ring.flush(reraise=sys.exc_info()[0] is None and sink_failed_on is None and not ring.defer_errors)
-            timing['sink'] = ring.sink_seconds
-            timing['ring_alloc'] = ring.alloc_seconds
-        if paf_ring is not None:
-            paf_ring.flush(reraise=sys.exc_info()[0] is None and sink_failed_on is None and not paf_ring.defer_errors)
+        quiet = unwinding or self.sink_failed_on is not None      # in a multi-rank run a sink's error is reported by raise_outcome
+        if self.ring is not None:
+            self.ring.flush(reraise=not quiet and not self.ring.defer_errors)
+            timing['sink'] = self.ring.sink_seconds
+            timing['ring_alloc'] = self.ring.alloc_seconds
+        if self.paf_ring is not None:
+            self.paf_ring.flush(reraise=not quiet and not self.paf_ring.defer_errors)
         timing['flush'] = time.perf_counter() - t0
         timing['retries'] = sum(getattr(e, 'retries', 0) for e in pool.engines if e is not None)
         timing['device_batch_seconds_avg'] = pool.job_seconds / max(pool.job_count, 1.0)
         timing['wait_for_engine'] = pool.wait_engine_seconds
         timing['engines'] = len(pool.engines)
-        timing['run_batches_seconds'] = time.perf_counter() - t_job
+        timing['run_batches_seconds'] = time.perf_counter() - self.t_job
         timing['create_clones_thread_seconds'] = pool.create_seconds
-        if pool.create_errors and shard.rank == 0:
+        if pool.create_errors and self.shard.rank == 0:
             print(f'\n  {len(pool.create_errors)} of the {len(pool.engines) - 1} extra batch engines could not be created '
-                  f'({pool.create_errors[0]}): the job ran on fewer', file=output)
-    if shard.rank == 0:
-        print('\n', file=output)
-    if ring is not None and ring.error is not None and (sink_failed_on is not None or ring.defer_errors):
-        raise ring.error                     # this rank's own sink
-    if paf_ring is not None and paf_ring.error is not None and (sink_failed_on is not None or paf_ring.defer_errors):
-        raise paf_ring.error                 # this rank's own PAF file
-    if sink_failed_on is not None:
-        sys.exit(f'Error: the output of rank {sink_failed_on} failed; every rank stopped at the same batch')
-    if fatal:
-        sys.exit(NOFRAG_MESSAGE)
-    if bad_read is not None:
-        sys.exit(f'Error: read {bad_read} exceeded an internal limit of the GPU path (status bits in its statistics); '
-                 'no output was written for it or any later read')
-    return count, total
+                  f'({pool.create_errors[0]}): the job ran on fewer', file=self.output)
+
+    def raise_outcome(self):
+        """The ways out other than a count: this rank's own sink, another rank's sink, no fragment, a read beyond the GPU path's limits."""
+        for ring in (self.ring, self.paf_ring):      # this rank's own sink, then its own PAF file
+            if ring is not None and ring.error is not None and (self.sink_failed_on is not None or ring.defer_errors):
+                raise ring.error
+        if self.sink_failed_on is not None:
+            sys.exit(f'Error: the output of rank {self.sink_failed_on} failed; every rank stopped at the same batch')
+        if self.fatal:
+            sys.exit(NOFRAG_MESSAGE)
+        if self.bad_read is not None:
+            sys.exit(f'Error: read {self.bad_read} exceeded an internal limit of the GPU path (status bits in its statistics); '
+                     'no output was written for it or any later read')
 
 
 def expected_error_rate(identities):
     """Mean errors per base of the job's identity law (beta: 1 - mean; qscore-normal: E[10^(-q / 10)]): what the traceback stores of
     a batch grow with (engine.presize)."""
-    import math
     if identities.type == 'beta':
         return min(max(1.0 - float(identities.mean), 0.0), 1.0)
     sigma = float(identities.stdev) * math.log(10.0) / 10.0
@@ -949,8 +944,6 @@ class _PartsLog(object):
     counter stands at the end of that batch's last gzip member."""
 
     def __init__(self, parts_file, zparts_file=None, sink_bytes_out=None):
-        import collections
-        import threading
         self.parts_file, self.zparts_file, self.sink_bytes_out = parts_file, zparts_file, sink_bytes_out
         self.lock = threading.Lock()
         self.ends = collections.deque()
@@ -975,6 +968,86 @@ class _PartsLog(object):
                 z = int(self.sink_bytes_out())
                 self.zparts_file.write(f'{z - self.z_before}\n')
                 self.z_before = z
+
+
+class _Outputs(object):
+    """Where a rank's bytes go (open_outputs): `write` to rank 0's stdout (through --gzip's sink if asked for); with --output-shards
+    `local_write` and `local_parts`, this rank's own file and parts log; with --truth-paf `paf_write`.  None where not in use."""
+    local_write = local_parts = paf_write = None
+
+    def __init__(self, sink):
+        self.sink, self.files = sink, []
+
+    def write(self, part):
+        if self.sink is not None:
+            self.sink.write(memoryview(part))
+        else:                                   # a text-only stdout (e.g. captured in tests)
+            sys.stdout.write(bytes(part).decode('latin-1'))
+
+    def flush(self):
+        if self.sink is not None and hasattr(self.sink, 'flush'):
+            self.sink.flush()
+
+    def close(self):
+        for f in self.files:
+            f.close()
+
+
+def open_outputs(args, shard, engine, stdout):
+    """The sinks of one job.  Exits where the options exclude each other or, agreed between the ranks, where a rank cannot open its files."""
+    sink = stdout if stdout is not None else getattr(sys.stdout, 'buffer', None)
+    gzip_level = getattr(args, 'gzip_level', None)
+    device_gzip = bool(getattr(args, 'gzip_device', False))
+    if device_gzip and gzip_level is not None:
+        sys.exit('Error: --gzip and --gzip-device exclude each other')
+    if gzip_level is not None and sink is not None and shard.rank == 0:
+        from .output import GzipSink
+        sink = GzipSink(sink, gzip_level)          # multi-threaded gzip members (libbrx_host.so)
+    outs = _Outputs(sink)
+    # --output-shards PREFIX: every rank writes PREFIX.<rank>.fastq[.gz] itself (and the bytes per batch to PREFIX.<rank>.parts), so that N ranks
+    # leave through N PCIe links and N files instead of rank 0's one of each (simulate.py:77-82 is one print loop).  .parts counts what the rank handed
+    # to its sink per batch: FASTQ text (also with --gzip, whose .zparts holds the same batches' compressed bytes), compressed bytes with --gzip-device.
+    prefix = getattr(args, 'output_shards', None)
+    if prefix:
+        open_error = zparts_file = None
+        try:                                # a rank that cannot open its files must not leave the others in their first exchange
+            shard_file = open(f'{prefix}.{shard.rank}.fastq' + ('.gz' if device_gzip or gzip_level is not None else ''), 'wb')
+            outs.files.append(shard_file)
+            parts_file = open(f'{prefix}.{shard.rank}.parts', 'w')
+            outs.files.append(parts_file)
+            if gzip_level is not None:
+                zparts_file = open(f'{prefix}.{shard.rank}.zparts', 'w')
+                outs.files.append(zparts_file)
+        except OSError as ex:
+            open_error = ex
+        failed = shard.gather_word(1 if open_error else 0)
+        if any(failed):
+            outs.close()
+            shard.finish()
+            sys.exit(f'Error: could not open the output shards of rank(s) {[r for r, x in enumerate(failed) if x]}'
+                     + (f': {open_error}' if open_error else ''))
+        shard_sink = shard_file
+        if gzip_level is not None:
+            from .output import GzipSink
+            shard_sink = GzipSink(shard_file, gzip_level)
+        log = _PartsLog(parts_file, zparts_file, (lambda: shard_sink.bytes_out) if zparts_file is not None else None)
+
+        def local_write(part):
+            shard_sink.write(memoryview(part))
+            log.wrote(len(part))
+        outs.local_write, outs.local_parts = local_write, log.batch
+    # --truth-paf PATH: the truth alignments of the reads (brx_emit_paf), plain text; with --output-shards every rank writes
+    # PATH.<rank>, the records of the reads of its own FASTQ file
+    truth_paf = getattr(args, 'truth_paf', None)
+    if truth_paf:
+        if not hasattr(engine, 'emit_paf_device'):
+            shard.finish()
+            sys.exit('Error: --truth-paf needs the GPU engine')
+        if prefix or shard.rank == 0:
+            paf_file = open(f'{truth_paf}.{shard.rank}' if prefix else truth_paf, 'wb')
+            outs.files.append(paf_file)
+            outs.paf_write = paf_file.write
+    return outs
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1031,86 +1104,15 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
     engine.set_params(sim_params_from_args(args, frag_lengths, identities, start_rate, start_amount,
                                            end_rate, end_amount))
     mark('tables_on_device')
-    sink = stdout if stdout is not None else getattr(sys.stdout, 'buffer', None)
-    gzip_level = getattr(args, 'gzip_level', None)
-    device_gzip = bool(getattr(args, 'gzip_device', False))
-    if device_gzip and gzip_level is not None:
-        sys.exit('Error: --gzip and --gzip-device exclude each other')
-    if gzip_level is not None and sink is not None and shard.rank == 0:
-        from .output import GzipSink
-        sink = GzipSink(sink, gzip_level)          # multi-threaded gzip members (libbrx_host.so)
-    if sink is not None:
-        def write(part):
-            sink.write(memoryview(part))
-    else:                                   # a text-only stdout (e.g. captured in tests)
-        def write(part):
-            sys.stdout.write(bytes(part).decode('latin-1'))
-    # --output-shards PREFIX: every rank writes PREFIX.<rank>.fastq[.gz] itself (and the bytes per batch to PREFIX.<rank>.parts),
-    # so that N ranks leave through N PCIe links and N files instead of rank 0's one of each (simulate.py:77-82 is one print loop)
-    #   PREFIX.<rank>.parts: one line per batch = the bytes this rank handed to its sink for that batch -- FASTQ text for the plain
-    #   file and for --gzip (whose file holds that text as gzip members), compressed bytes for --gzip-device (the members are made
-    #   on the GPU, batch by batch).  With --gzip, PREFIX.<rank>.zparts holds the compressed bytes per batch beside it (every batch
-    #   ends a gzip member), so that the .gz files too can be put back in read order without decompressing them.
-    local_write = local_parts = None
-    files = []
-    prefix = getattr(args, 'output_shards', None)
-    if prefix:
-        zipped = device_gzip or gzip_level is not None
-        open_error = None
-        try:                                # a rank that cannot open its files must not leave the others in their first exchange
-            shard_file = open(f'{prefix}.{shard.rank}.fastq' + ('.gz' if zipped else ''), 'wb')
-            files.append(shard_file)
-            parts_file = open(f'{prefix}.{shard.rank}.parts', 'w')
-            files.append(parts_file)
-            zparts_file = None
-            if gzip_level is not None:
-                zparts_file = open(f'{prefix}.{shard.rank}.zparts', 'w')
-                files.append(zparts_file)
-        except OSError as ex:
-            open_error = ex
-        failed = [int(x[0]) for x in shard.gather_words(np.array([1 if open_error else 0], dtype=np.uint32), [1] * shard.world)]
-        if any(failed):
-            for f in files:
-                f.close()
-            shard.finish()
-            sys.exit(f'Error: could not open the output shards of rank(s) {[r for r, x in enumerate(failed) if x]}'
-                     + (f': {open_error}' if open_error else ''))
-        shard_sink = shard_file
-        if gzip_level is not None:
-            from .output import GzipSink
-            shard_sink = GzipSink(shard_file, gzip_level)
-        log = _PartsLog(parts_file, zparts_file, (lambda: shard_sink.bytes_out) if zparts_file is not None else None)
-
-        def local_write(part):
-            shard_sink.write(memoryview(part))
-            log.wrote(len(part))
-
-        local_parts = log.batch
-    # --truth-paf PATH: the truth alignments of the reads (brx_emit_paf), plain text; with --output-shards every rank writes
-    # PATH.<rank>, the records of the reads of its own FASTQ file
-    truth_paf = getattr(args, 'truth_paf', None)
-    paf_write = None
-    if truth_paf:
-        if not hasattr(engine, 'emit_paf_device'):
-            shard.finish()
-            sys.exit('Error: --truth-paf needs the GPU engine')
-        if prefix or shard.rank == 0:
-            paf_file = open(f'{truth_paf}.{shard.rank}' if prefix else truth_paf, 'wb')
-            files.append(paf_file)
-
-            def paf_write(part):
-                paf_file.write(part)
+    outs = open_outputs(args, shard, engine, stdout)
     try:
         try:
-            result = run_batches(engine, seed, target_size, float(args.mean_frag_length), write, quiet, shard,
-                                 in_flight=getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, device_gzip=device_gzip,
-                                 local_write=local_write, local_parts=local_parts, expected_error=expected_error_rate(identities), arenas=arenas,
-                                 truth_paf=bool(truth_paf), paf_write=paf_write)
-            if prefix and hasattr(shard_sink, 'flush') and shard_sink is not shard_file:
-                shard_sink.flush()
+            result = run_batches(engine, seed, target_size, float(args.mean_frag_length), outs.write, quiet, shard,
+                                 in_flight=getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, device_gzip=bool(getattr(args, 'gzip_device', False)),
+                                 local_write=outs.local_write, local_parts=outs.local_parts, expected_error=expected_error_rate(identities),
+                                 arenas=arenas, truth_paf=bool(getattr(args, 'truth_paf', None)), paf_write=outs.paf_write)
         finally:
-            for f in files:
-                f.close()
+            outs.close()
     except (SystemExit, OSError):
         shard.finish()                      # exits every rank takes at the same batch: NOFRAG, a bad read, a failed sink
         raise
@@ -1121,8 +1123,7 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
         shard.abandon()
         raise
     shard.finish()
-    if sink is not None and hasattr(sink, 'flush'):
-        sink.flush()
+    outs.flush()
     if os.environ.get('BRX_DRIVER_TIMING') and shard.rank == 0:      # seconds of the consumer thread per activity + rate, for tools/cli_30x.sh
         t = dict(run_batches.last_timing)
         t['bases'], t['reads'] = result[1], result[0]
@@ -1145,8 +1146,7 @@ class _Null(object):
 
 def _broadcast_seed(shard, seed):
     import torch
-    dev = torch.device('cuda', torch.cuda.current_device()) if shard.dist.get_backend() == 'nccl' else torch.device('cpu')
-    t = torch.tensor([seed], dtype=torch.int64, device=dev)
+    t = torch.tensor([seed], dtype=torch.int64, device=shard._device())
     shard.dist.broadcast(t, src=0)
     return int(t.item())
 

@@ -131,6 +131,153 @@ def test_cut_point_and_plan_batch():
     assert sh.slice_of(100, 10) == (105, 5) and S.Shard(0, 2).slice_of(100, 9) == (100, 5) and sh.slice_of(100, 9) == (105, 4)
 
 
+def _stats(seq_len, status=None, skipped=()):
+    """Per-read statistics as the engines give them, for reads of these lengths: records of seq_len + 50 bytes one behind the
+    other, none for the reads listed in `skipped`."""
+    from badread_amd.engine import READ_STATS_DTYPE
+    st = np.zeros(len(seq_len), dtype=READ_STATS_DTYPE)
+    st['seq_len'] = seq_len
+    st['rec_len'] = st['seq_len'] + 50
+    st['rec_len'][list(skipped)] = 0
+    st['rec_off'] = np.cumsum(st['rec_len']) - st['rec_len']
+    if status is not None:
+        st['status'] = status
+    return st
+
+
+def _random_words(rng, n):
+    """Exchanged words of n reads: lengths (a few of them 0), a NOFRAG or BAD bit on about one read in thirty."""
+    words = (rng.randint(1, 60, n) * (rng.rand(n) > 0.15)).astype(np.uint32)
+    words[rng.rand(n) < 0.02] |= np.uint32(S.FLAG_NOFRAG)
+    words[rng.rand(n) < 0.02] |= np.uint32(S.FLAG_BAD)
+    return words
+
+
+def test_exchange_words():
+    from badread_amd.engine import RS_BAND, RS_EMPTY, RS_NOFRAG, RS_QMISS, RS_TOO_MANY_SEGS
+    st = _stats([10, 20, 30, 40, 50, 60], status=[0, RS_NOFRAG, RS_BAND, RS_EMPTY, RS_QMISS | RS_NOFRAG, RS_TOO_MANY_SEGS], skipped=[3])
+    words = S.exchange_words(st)
+    assert words.dtype == np.uint32
+    assert words.tolist() == [10, 20 | S.FLAG_NOFRAG, 30 | S.FLAG_BAD, 0, 50 | S.FLAG_NOFRAG | S.FLAG_BAD, 60 | S.FLAG_BAD]
+    assert S.exchange_words(st[:0]).shape == (0,)
+    with pytest.raises(AssertionError):                     # a length that would run into the status bits
+        S.exchange_words(_stats([S.FLAG_BAD]))
+    rng = np.random.RandomState(11)
+    for _ in range(1000):                                   # against the lines this function was cut out of
+        n = rng.randint(0, 40)
+        st = _stats(rng.randint(0, 5000, n), status=rng.choice([0, 0, 0, 1, 2, 4, 8, 16, 5], n), skipped=np.flatnonzero(rng.rand(n) < 0.2))
+        ref = (st['seq_len'].astype(np.uint32) * (st['rec_len'] > 0)).astype(np.uint32)
+        ref |= np.where(st['status'] & RS_NOFRAG, S.FLAG_NOFRAG, 0).astype(np.uint32)
+        ref |= np.where(st['status'] & S.BAD_STATUS, S.FLAG_BAD, 0).astype(np.uint32)
+        assert (S.exchange_words(st) == ref).all()
+
+
+def _stop_block_of_the_loop(allw, base, total, target_size, n_super):
+    """The stop rule as the read loop spelled it out before stop_decision existed, restated as the reference."""
+    fatal = bad_read = None
+    lens = (allw & (S.FLAG_BAD - 1)).astype(np.int64)
+    cut = S.cut_point(lens, total, target_size)
+    wrong = np.flatnonzero(allw & (S.FLAG_NOFRAG | S.FLAG_BAD))
+    stop_at = None
+    if len(wrong) and (cut is None or wrong[0] < cut):
+        stop_at = int(wrong[0])
+        if allw[stop_at] & S.FLAG_NOFRAG:
+            fatal = True
+        else:
+            bad_read = base + stop_at
+    last = stop_at - 1 if stop_at is not None else (cut if cut is not None else n_super - 1)
+    return last, bool(fatal), bad_read
+
+
+def test_stop_decision():
+    w = lambda *v: np.array(v, dtype=np.uint32)
+    BAD, NOFRAG = S.FLAG_BAD, S.FLAG_NOFRAG
+    assert S.stop_decision(w(10, 0, 5, 7, 9), 100, 0, 15) == (2, False, None)                  # a cut, nothing wrong
+    assert S.stop_decision(w(10, 0, 5, 7, 9), 100, 5, 100) == (4, False, None)                 # no cut: the whole batch
+    assert S.stop_decision(w(10, 5 | BAD, 5, 7), 100, 0, 20) == (0, False, 101)                # a bad read before the cut
+    assert S.stop_decision(w(10, 5, 5 | BAD, 7), 100, 0, 20) == (2, False, None)               # AT the cut: the cut read is kept, not looked at
+    assert S.stop_decision(w(10, 5, 5, 7 | BAD), 100, 0, 20) == (2, False, None)               # behind the cut: ignored
+    assert S.stop_decision(w(10, 5, 5, NOFRAG), 100, 0, 20) == (2, False, None)
+    assert S.stop_decision(w(10, NOFRAG, 5, 7), 100, 0, 20) == (0, True, None)                 # NOFRAG before the cut: fatal
+    assert S.stop_decision(w(10, 3 | NOFRAG | BAD, 5, 7), 100, 0, 20) == (0, True, None)       # both bits: NOFRAG decides
+    assert S.stop_decision(w(0, 0, 0), 100, 50, 20) == (2, False, None)                        # empty reads only: no cut, last = n_super - 1
+    assert S.stop_decision(w(BAD | 4, 10, 10), 100, 0, 15) == (-1, False, 100)                 # a bad word at index 0: nothing is kept
+    assert S.stop_decision(w(NOFRAG, 10, 10), 100, 0, 15) == (-1, True, None)
+    rng = np.random.RandomState(12)
+    for _ in range(1000):
+        n = rng.randint(1, 50)
+        allw, base, total = _random_words(rng, n), int(rng.randint(0, 10 ** 6)), int(rng.randint(0, 500))
+        target = total + int(rng.randint(1, 1500))
+        got = S.stop_decision(allw, base, total, target)
+        assert got == _stop_block_of_the_loop(allw, base, total, target, n), (allw, base, total, target)
+        assert isinstance(got[0], int) and isinstance(got[1], bool)
+
+
+def test_kept_bytes():
+    st = _stats([10, 20, 30, 40])                           # records of 60, 70, 80, 90 bytes
+    # three ranks of a 12-read super-batch that starts at read 100, last kept position 5: reads 100 .. 105
+    assert S.kept_bytes(st, 100, 100, 5, 4) == (4, 300)                                        # wholly before `last`
+    assert S.kept_bytes(st, 104, 100, 5, 4) == (2, 130)                                        # straddles it
+    assert S.kept_bytes(st, 108, 100, 5, 4) == (0, 0)                                          # wholly after it
+    assert S.kept_bytes(st, 100, 100, -1, 4) == (0, 0) and S.kept_bytes(st[:0], 112, 100, 5, 0) == (0, 0)
+    assert S.kept_bytes(_stats([10, 20, 30], skipped=[1]), 100, 100, 1, 3) == (2, 60)          # a skipped read has no bytes
+    rng = np.random.RandomState(13)
+    for _ in range(1000):                                   # against the lines this function was cut out of
+        n_mine = rng.randint(0, 30)
+        st = _stats(rng.randint(0, 5000, n_mine), skipped=np.flatnonzero(rng.rand(n_mine) < 0.2))
+        base = int(rng.randint(0, 10 ** 6))
+        first, last = base + int(rng.randint(0, 60)), int(rng.randint(-1, 90))
+        keep = int(np.clip(last - (first - base) + 1, 0, n_mine))
+        my_bytes = int(st['rec_off'][keep - 1] + st['rec_len'][keep - 1]) if keep else 0
+        assert S.kept_bytes(st, first, base, last, n_mine) == (keep, my_bytes)
+
+
+def test_engines_for_memory_is_the_rule_of_both_callers():
+    """The cases of test_batches_in_flight_follow_the_free_device_memory against the pure rule (the first engine's arena is
+    mapped: arenas_held = 1), and for the arenas requested ahead (none mapped yet: arenas_held = 0) the inequality that
+    _ArenaPrefetch.for_job spelled out, n * nbytes + (2 n + 2) * out_bytes + reserve > free."""
+    GB = 1 << 30
+    fit = S.engines_for_memory
+    for free, reserve, expect in ((247, 24, 5), (260, 24, 6), (10, 24, 1), (229, 0, 6)):
+        assert fit(free * GB, 6, 40 * GB, 1, 2 * GB, reserve * GB) == expect
+        n = 6
+        while n > 1 and n * 40 * GB + (2 * n + 2) * 2 * GB + reserve * GB > free * GB:
+            n -= 1
+        assert fit(free * GB, 6, 40 * GB, 0, 2 * GB, reserve * GB) == n
+    assert fit(288 * GB, 6, 40 * GB, 0, 2 * GB, 24 * GB) == 5 and fit(292 * GB, 6, 40 * GB, 0, 2 * GB, 24 * GB) == 6
+    assert fit(10 ** 15, 3, 40 * GB, 0, 2 * GB, 24 * GB) == 3          # never more than asked for
+    rng = np.random.RandomState(14)
+    for _ in range(1000):                                   # both callers' loops, as they stood
+        free, wanted = int(rng.randint(0, 300)) * GB, int(rng.randint(1, 9))
+        arena, out, reserve = int(rng.randint(0, 60 * 1024)) << 20, int(rng.randint(0, 4096)) << 20, int(rng.randint(0, 30)) * GB
+        n = wanted
+        while n > 1 and (n - 1) * arena + (2 * n + 2) * out + reserve > free:
+            n -= 1
+        assert fit(free, wanted, arena, 1, out, reserve) == n
+        n = wanted
+        while n > 1 and n * arena + (2 * n + 2) * out + reserve > free:
+            n -= 1
+        assert fit(free, wanted, arena, 0, out, reserve) == n
+
+
+def test_driver_reserve_and_expected_out_bytes(monkeypatch):
+    from badread_amd.engine import PAF_SHARE
+    monkeypatch.delenv('BRX_DRIVER_RESERVE_GB', raising=False)
+    assert S.driver_reserve_bytes() == 24 << 30
+    monkeypatch.setenv('BRX_DRIVER_RESERVE_GB', '0.5')
+    assert S.driver_reserve_bytes() == 1 << 29
+
+    class Knows(object):
+        def expected_record_bytes(self):
+            return 34000.0
+    # an engine without an estimate of its own (and None): 2.1 B per base + 400 per read
+    assert S.expected_out_bytes(object(), 1000, 15000.0, False) == S.expected_out_bytes(None, 1000, 15000.0, False) == 31900000
+    assert S.expected_out_bytes(Knows(), 1000, 15000.0, False) == 34000000
+    assert S.expected_out_bytes(Knows(), 1000, 15000.0, True) == int(34000000 * (1.0 + PAF_SHARE))
+    assert S.expected_out_bytes(None, 4096, 15000.0, True) == int(4096 * (2.1 * 15000.0 + 400.0) * (1.0 + PAF_SHARE))
+    assert S.Shard().gather_word(7) == [7] and not S._on_gpu(object()) and not S._on_gpu(None)
+
+
 WORKER = r'''
 import io, os, sys
 sys.path[:0] = [{repo!r}, {repo!r} + '/oracle', {repo!r} + '/tests']
