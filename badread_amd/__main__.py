@@ -88,6 +88,11 @@ SIMULATE_OPTIONS = [
                              help='Also write the true alignment of every read against the reference to PATH as PAF (plain text): '
                                   'one record per stretch of the read that comes consecutively from one contig and strand, with a '
                                   'cg:Z: CIGAR; with --output-shards every rank writes PATH.<rank>')),
+        ('--truth-sam', dict(type=str, default=None, dest='truth_sam', metavar='PATH',
+                             help='Also write the same true alignments to PATH as SAM (plain text, with header): one line per PAF '
+                                  'record, the whole read with SEQ, QUAL and the FASTQ header (CO:Z:) on the primary line, the '
+                                  'record\'s slice on the supplementary ones, one unmapped line for a read with no record; can be '
+                                  'combined with --truth-paf; with --output-shards every rank writes PATH.<rank>')),
         ('--gpu-streams', dict(type=int, default=None, dest='gpu_streams',
                                help='Device batches in flight per GPU, each on its own HIP stream (default: 6)')),
     ]),
@@ -165,9 +170,10 @@ def check_simulate_args(args):
     """Validate and derive the fields simulate() reads (mean_frag_length, identity triple, glitch_*)."""
     if not pathlib.Path(args.reference).is_file():
         sys.exit(f'Error: {args.reference} is not a file')
-    truth_paf = getattr(args, 'truth_paf', None)
-    if truth_paf is not None and not pathlib.Path(truth_paf).resolve().parent.is_dir():
-        sys.exit(f'Error: the directory of --truth-paf {truth_paf} does not exist')
+    for flag in ('truth_paf', 'truth_sam'):
+        path = getattr(args, flag, None)
+        if path is not None and not pathlib.Path(path).resolve().parent.is_dir():
+            sys.exit(f'Error: the directory of --{flag.replace("_", "-")} {path} does not exist')
     for value, names, flag in ((args.error_model, ERROR_MODEL_NAMES, '--error_model'),
                                (args.qscore_model, QSCORE_MODEL_NAMES, '--qscore_model')):
         if value.lower() not in names and not pathlib.Path(value).is_file():

@@ -22,6 +22,7 @@
 #include "brx_kernels.h"
 #include "brx_finplan.h"
 #include "brx_paf.h"
+#include "brx_sam.h"
 
 #define BRX_KEV_MAX 2048
 
@@ -75,10 +76,11 @@ struct brx_ctx {
     int kev_n, kev_dropped;
     brx_kernel_stat kstat[BRX_KERN_COUNT];
     int profile;                 /* BRX_PROFILE=1: the mutate kernels time their phases (brx_last_phase_cycles) */
-    /* brx_emit_paf: what the last brx_simulate_batch left in the arena (valid until the next call that reuses the arena) */
+    /* brx_emit_paf / brx_emit_sam: what the last brx_simulate_batch left in the arena (valid until the next call that reuses the arena) */
     bool paf_valid;
     BrxDev paf_dev;
     const RS *paf_rs; const PSeg *paf_segs; uint32_t paf_reads;
+    const PPiece *paf_pieces; const uint8_t *paf_seqbuf;      /* brx_emit_sam: what k_emit read the records from */
     uint8_t *h_paf, *d_paf; size_t paf_bytes;      /* pinned (mapped): per-read PAF bytes, primary records and offsets */
     char err[512];
 };
@@ -1054,7 +1056,7 @@ int Batch::run() {
     if ((rc = records())) return rc;
     if (c->ktiming && (rc = kernel_statistics())) return rc;
     if (out_bytes) *out_bytes = (size_t)rec_bytes;
-    if (!raw) { c->paf_dev = dev; c->paf_rs = rs; c->paf_segs = segs; c->paf_reads = n_reads; c->paf_valid = true; }
+    if (!raw) { c->paf_dev = dev; c->paf_rs = rs; c->paf_segs = segs; c->paf_reads = n_reads; c->paf_pieces = pieces; c->paf_seqbuf = c->scratch; c->paf_valid = true; }
     /* a read that exhausted its 1000 tries is fatal in the reference (simulate.py:164) */
     if (!raw) {
         { int rc_ = fetch_rs(st); if (rc_) return rc_; }
@@ -1249,8 +1251,8 @@ extern "C" int brx_gzip_device(brx_ctx *c, const void *d_in, size_t n_bytes, con
     return BRX_OK;
 }
 
-/* ---- truth alignments of the last simulate batch (brx_paf.h) ---- */
-extern "C" int brx_emit_paf(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+/* ---- truth alignments of the last simulate batch: PAF text (brx_paf.h) or SAM records (brx_sam.h) ---- */
+static int emit_truth(brx_ctx *c, bool sam, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
     if (!c || !out_bytes) return BRX_E_ARG;
     *out_bytes = 0;
     if (!c->paf_valid) return fail(c, BRX_E_STATE, "no simulate batch on this context to emit truth alignments for");
@@ -1268,20 +1270,31 @@ extern "C" int brx_emit_paf(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t
     }
     uint32_t *len = (uint32_t *)(c->d_paf + len_at), *best = (uint32_t *)(c->d_paf + best_at);
     uint64_t *off = (uint64_t *)(c->d_paf + off_at);
-    if (n) hipLaunchKernelGGL(k_paf_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, (const uint8_t *)c->scratch, len, best);
-    hipLaunchKernelGGL(k_paf_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
-    { int rcw = wait_stream(c, st, "k_paf_size"); if (rcw) return rcw; }
+    const uint8_t *arena = (const uint8_t *)c->scratch;
+    if (n && sam) hipLaunchKernelGGL(k_sam_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best);
+    else if (n) hipLaunchKernelGGL(k_paf_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best);
+    if (sam) hipLaunchKernelGGL(k_sam_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
+    else hipLaunchKernelGGL(k_paf_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
+    { int rcw = wait_stream(c, st, sam ? "k_sam_size" : "k_paf_size"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
     const uint64_t total = ((const uint64_t *)(c->h_paf + off_at))[n];
     if (total > out_cap || (total && !d_out)) {
         c->output_needed = total;
         return fail(c, BRX_E_OUTPUT, "truth alignment buffer too small: need %llu bytes", (unsigned long long)total);
     }
-    if (n && total) hipLaunchKernelGGL(k_paf_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, (const uint8_t *)c->scratch,
-                                       (const uint64_t *)off, (const uint32_t *)best, d_out);
+    if (n && total && sam) hipLaunchKernelGGL(k_sam_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf,
+                                              (const uint64_t *)off, (const uint32_t *)best, d_out);
+    else if (n && total) hipLaunchKernelGGL(k_paf_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena,
+                                            (const uint64_t *)off, (const uint32_t *)best, d_out);
     if (d_read_off) HIPCHK(c, hipMemcpyAsync(d_read_off, c->h_paf + off_at, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-    { int rcw = wait_stream(c, st, "k_paf_write"); if (rcw) return rcw; }
+    { int rcw = wait_stream(c, st, sam ? "k_sam_write" : "k_paf_write"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
     *out_bytes = (size_t)total;
     return BRX_OK;
+}
+extern "C" int brx_emit_paf(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+    return emit_truth(c, false, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+}
+extern "C" int brx_emit_sam(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+    return emit_truth(c, true, d_out, out_cap, d_read_off, out_bytes, hip_stream);
 }

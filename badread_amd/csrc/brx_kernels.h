@@ -1385,10 +1385,9 @@ __device__ void put_uuid(S &s, const BrxDev &d, uint64_t read) {
     put_hex(s, w[0], 8); s.put('-'); put_hex(s, w[1] >> 16, 4); s.put('-'); put_hex(s, w[1] & 0xFFFFu, 4); s.put('-');
     put_hex(s, w[2] >> 16, 4); s.put('-'); put_hex(s, w[2] & 0xFFFFu, 4); put_hex(s, w[3], 8);
 }
+/* the header line after "@name ", without its newline: the FASTQ header and the CO:Z: tag of the SAM lines (brx_sam.h) */
 template <class S>
-__device__ void put_header(S &s, const BrxDev &d, uint64_t read, const RS &r, const PPiece *pieces) {
-    s.put('@');
-    put_uuid(s, d, read); s.put(' ');
+__device__ void put_comment(S &s, const BrxDev &d, const RS &r, const PPiece *pieces) {
     for (uint32_t i = 0; i < r.n_pieces; ++i) {
         const PPiece pc = pieces[r.piece_off + i];
         uint32_t type = pc.w0 & 3u, strand = (pc.w0 >> 2) & 1u, contig = pc.w0 >> 3;
@@ -1412,7 +1411,14 @@ __device__ void put_header(S &s, const BrxDev &d, uint64_t read, const RS &r, co
     put_dec(s, mr / 1000); s.put('.');
     uint32_t fr = (uint32_t)(mr % 1000);
     s.put((uint8_t)('0' + fr / 100)); s.put((uint8_t)('0' + (fr / 10) % 10)); s.put((uint8_t)('0' + fr % 10));
-    s.put('%'); s.put('\n');
+    s.put('%');
+}
+template <class S>
+__device__ void put_header(S &s, const BrxDev &d, uint64_t read, const RS &r, const PPiece *pieces) {
+    s.put('@');
+    put_uuid(s, d, read); s.put(' ');
+    put_comment(s, d, r, pieces);
+    s.put('\n');
 }
 
 __global__ void __launch_bounds__(64) k_recsize(BrxDev d, RS *rs, const PPiece *pieces) {

@@ -18,15 +18,13 @@
  *              sink, writes it (a second sweep: every lane that ends a CIGAR run places its text with a wave prefix sum;
  *              '-' records mirror the runs, the convention of minimap2 that alignment.py undoes)
  * The same code sizes (PafCount) and writes (PafWrite): k_paf_size / k_paf_scan / k_paf_write, the pattern of
- * k_recsize / k_scan_rec / k_emit.
+ * k_recsize / k_scan_rec / k_emit.  The walk hands every record to its sink (sink.record), so brx_sam.h walks the same records.
  */
 #ifndef BRX_PAF_H
 #define BRX_PAF_H
 
 #define BRX_PAF_NOKEY (~0ull)          /* no origin: pads, adapters, junk, random sequence, glitch inserts */
 
-struct PafCount { static constexpr bool write = false; uint8_t *out; };
-struct PafWrite { static constexpr bool write = true; uint8_t *out; };
 
 __device__ __forceinline__ uint32_t paf_digits(uint32_t v) { uint32_t n = 1; while (v >= 10) { v /= 10; ++n; } return n; }
 __device__ __forceinline__ int paf_top(uint64_t bits) { return 63 - __builtin_clzll(bits); }     /* bits != 0 */
@@ -37,6 +35,18 @@ struct PafRead {                                                 /* what a recor
     const uint8_t *ops; uint64_t read; uint32_t seq_len, start_trim;
     uint32_t best;                   /* the primary record (writing sink: found by the sizing pass) */
     uint32_t n_rec, top, top_set; int64_t top_as; uint64_t at;      /* records so far, the first of the highest AS among them */
+};
+struct PafShape { uint32_t cnt[4], text; };                      /* a record's columns by op, the text length of its CIGAR */
+
+/* The sinks of the walk (paf_read): what is done with every record it closes.  brx_sam.h adds its own two. */
+template <class S> __device__ void paf_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q);
+struct PafCount {
+    static constexpr bool write = false; uint8_t *out;
+    __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { paf_record(*this, d, R, q); }
+};
+struct PafWrite {
+    static constexpr bool write = true; uint8_t *out;
+    __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { paf_record(*this, d, R, q); }
 };
 
 /* The header fields of a record (qname .. cg:Z:) and its tail (\tNM:i:..\tAS:i:..\n). */
@@ -56,21 +66,20 @@ __device__ void paf_head(B &b, const BrxDev &d, const PafRead &R, const PafRec &
     put_dec(b, n_eq); b.put('\t'); put_dec(b, cols); put_str(b, "\t60\ttp:A:"); b.put(primary ? 'P' : 'S'); put_str(b, "\tcg:Z:");
 }
 template <class B>
-__device__ void paf_tail(B &b, uint32_t nm, int64_t as) {
+__device__ void paf_tags(B &b, uint32_t nm, int64_t as) {
     put_str(b, "\tNM:i:"); put_dec(b, nm); put_str(b, "\tAS:i:");
     if (as < 0) { b.put('-'); put_dec(b, (uint64_t)(-as)); } else put_dec(b, (uint64_t)as);
-    b.put('\n');
 }
+template <class B>
+__device__ void paf_tail(B &b, uint32_t nm, int64_t as) { paf_tags(b, nm, as); b.put('\n'); }
 
-/* One record [q.c0, q.c1] of the read: sized, and written when S writes.  Every lane calls it (wave-uniform arguments). */
-template <class S>
-__device__ void paf_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q) {
+/* Sweep 1 over the record [q.c0, q.c1]: op counts and the CIGAR's text length.  A lane whose column ends a run (the next column
+   is another class, or the record ends) owns that run's text: its decimal length and the letter.  Every lane calls it. */
+__device__ PafShape paf_shape(const PafRead &R, const PafRec &q) {
     const int lane = lane_id();
     const uint64_t below = (1ull << lane) - 1ull;
-    uint32_t cnt[4] = {0, 0, 0, 0};
-    uint32_t text = 0, run_start = q.c0;
-    /* sweep 1: op counts and the CIGAR's text length.  A lane whose column ends a run (the next column is another class, or
-       the record ends) owns that run's text: its decimal length and the letter. */
+    PafShape sh; sh.cnt[0] = sh.cnt[1] = sh.cnt[2] = sh.cnt[3] = 0; sh.text = 0;
+    uint32_t run_start = q.c0;
     for (uint32_t b = q.c0; b <= q.c1; b += 64) {
         const uint32_t c = b + lane;
         const bool in = c <= q.c1;
@@ -83,59 +92,78 @@ __device__ void paf_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
         const uint64_t mine = rmask & (below | (1ull << lane));
         const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
         const uint32_t t = re ? paf_digits(c - s0 + 1) + 1u : 0u;
-        text += wave_sum(t);
-        for (uint32_t o = 0; o < 4; ++o) cnt[o] += (uint32_t)__popcll(__ballot(in && op == o));
+        sh.text += wave_sum(t);
+        for (uint32_t o = 0; o < 4; ++o) sh.cnt[o] += (uint32_t)__popcll(__ballot(in && op == o));
         if (rmask) run_start = b + (uint32_t)paf_top(rmask);
     }
+    return sh;
+}
+
+/* Sweep 2: every run's text at its place in cig[0, text); the prefix sum of the text lengths over the lanes gives it.  '-'
+   records mirror the runs. */
+__device__ void paf_cigar(const PafRead &R, const PafRec &q, uint8_t *cig, uint32_t text, bool minus) {
+    const int lane = lane_id();
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint32_t done = 0, run_start = q.c0;
+    for (uint32_t b = q.c0; b <= q.c1; b += 64) {
+        const uint32_t c = b + lane;
+        const bool in = c <= q.c1;
+        const uint32_t op = in ? R.ops[c] : 0u;
+        const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
+        const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
+        const bool rs = in && (c == q.c0 || paf_cls(prev) != paf_cls(op));
+        const bool re = in && (c == q.c1 || paf_cls(next) != paf_cls(op));
+        const uint64_t rmask = __ballot(rs);
+        const uint64_t mine = rmask & (below | (1ull << lane));
+        const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
+        const uint32_t len = c - s0 + 1u;
+        const uint32_t t = re ? paf_digits(len) + 1u : 0u;
+        const uint32_t incl = wave_incl_scan(t);
+        if (re) {
+            const uint32_t fwd = done + incl - t;
+            uint8_t *p = cig + (minus ? text - fwd - t : fwd);
+            uint32_t v = len;
+            for (uint32_t x = t - 1; x-- > 0;) { p[x] = (uint8_t)('0' + v % 10); v /= 10; }
+            const uint32_t cl = paf_cls(op);
+            p[t - 1] = (uint8_t)(cl == 0 ? 'M' : cl == 2 ? 'I' : 'D');
+        }
+        done += wave_bcast_u32(incl, 63);
+        if (rmask) run_start = b + (uint32_t)paf_top(rmask);
+    }
+}
+
+/* Counts the record in; true when it is the read's best so far: the first of the highest AS becomes the primary. */
+__device__ __forceinline__ bool paf_rank(PafRead &R, int64_t as) {
+    const bool top = !R.top_set || as > R.top_as;
+    if (top) { R.top_as = as; R.top = R.n_rec; R.top_set = 1; }
+    R.n_rec += 1;
+    return top;
+}
+
+/* One record [q.c0, q.c1] of the read: sized, and written when S writes.  Every lane calls it (wave-uniform arguments). */
+template <class S>
+__device__ void paf_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q) {
+    const PafShape sh = paf_shape(R, q);
+    const uint32_t *cnt = sh.cnt, text = sh.text;
     const uint32_t cols = q.c1 - q.c0 + 1u;
     const uint32_t nm = cnt[1] + cnt[2] + cnt[3];
     const int64_t as = (int64_t)cnt[0] - (int64_t)nm;
     const uint32_t qcols = cnt[0] + cnt[1] + cnt[2], tspan = cnt[0] + cnt[1] + cnt[3];
     const bool primary = S::write && R.n_rec == R.best;
-    if (!R.top_set || as > R.top_as) { R.top_as = as; R.top = R.n_rec; R.top_set = 1; }   /* the first of equals */
-    R.n_rec += 1;
+    paf_rank(R, as);
     CountSink hc; hc.n = 0;
     paf_head(hc, d, R, q, qcols, tspan, cnt[0], cols, primary);
     CountSink tc; tc.n = 0;
     paf_tail(tc, nm, as);
     if (S::write) {
         uint8_t *o = sink.out + R.at;
-        if (lane == 0) {
+        if (lane_id() == 0) {
             ByteSink h; h.p = o; h.n = 0;
             paf_head(h, d, R, q, qcols, tspan, cnt[0], cols, primary);
             ByteSink tl; tl.p = o + hc.n + text; tl.n = 0;
             paf_tail(tl, nm, as);
         }
-        uint8_t *cig = o + hc.n;
-        const bool minus = (q.key0 >> 32) & 1u;
-        /* sweep 2: every run's text at its place; the prefix sum of the text lengths over the lanes gives it */
-        uint32_t done = 0;
-        run_start = q.c0;
-        for (uint32_t b = q.c0; b <= q.c1; b += 64) {
-            const uint32_t c = b + lane;
-            const bool in = c <= q.c1;
-            const uint32_t op = in ? R.ops[c] : 0u;
-            const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
-            const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
-            const bool rs = in && (c == q.c0 || paf_cls(prev) != paf_cls(op));
-            const bool re = in && (c == q.c1 || paf_cls(next) != paf_cls(op));
-            const uint64_t rmask = __ballot(rs);
-            const uint64_t mine = rmask & (below | (1ull << lane));
-            const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
-            const uint32_t len = c - s0 + 1u;
-            const uint32_t t = re ? paf_digits(len) + 1u : 0u;
-            const uint32_t incl = wave_incl_scan(t);
-            if (re) {
-                const uint32_t fwd = done + incl - t;
-                uint8_t *p = cig + (minus ? text - fwd - t : fwd);
-                uint32_t v = len;
-                for (uint32_t x = t - 1; x-- > 0;) { p[x] = (uint8_t)('0' + v % 10); v /= 10; }
-                const uint32_t cl = paf_cls(op);
-                p[t - 1] = (uint8_t)(cl == 0 ? 'M' : cl == 2 ? 'I' : 'D');
-            }
-            done += wave_bcast_u32(incl, 63);
-            if (rmask) run_start = b + (uint32_t)paf_top(rmask);
-        }
+        paf_cigar(R, q, o + hc.n, text, ((q.key0 >> 32) & 1u) != 0);
     }
     R.at += hc.n + text + tc.n;
 }
@@ -198,7 +226,7 @@ __device__ void paf_read(S &sink, const BrxDev &d, const RS &s, uint32_t r, cons
             const uint64_t before = mm & ((1ull << L) - 1ull);
             const uint32_t r0 = wave_bcast_u32(rr, L);
             const uint64_t k0 = wave_bcast_u64(key, L);
-            if (open) { q.c1 = before ? b + (uint32_t)paf_top(before) : (uint32_t)last_m; paf_record(sink, d, R, q); }
+            if (open) { q.c1 = before ? b + (uint32_t)paf_top(before) : (uint32_t)last_m; sink.record(d, R, q); }
             q.c0 = b + (uint32_t)L; q.r0 = r0; q.key0 = k0; open = true;
         }
         if (mm) {
@@ -210,7 +238,7 @@ __device__ void paf_read(S &sink, const BrxDev &d, const RS &s, uint32_t r, cons
         if (tm) carry_key = wave_bcast_u64(key, paf_top(tm));
         r_base += (uint32_t)__popcll(qm); f_base += (uint32_t)__popcll(tm);
     }
-    if (open) { q.c1 = (uint32_t)last_m; paf_record(sink, d, R, q); }
+    if (open) { q.c1 = (uint32_t)last_m; sink.record(d, R, q); }
 }
 
 __device__ __forceinline__ bool paf_has_records(const RS &s) {

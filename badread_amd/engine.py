@@ -80,6 +80,8 @@ assert READ_STATS_DTYPE.itemsize == 64
 RS_NOFRAG, RS_TOO_MANY_SEGS, RS_BAND, RS_QMISS, RS_EMPTY = 1, 2, 4, 8, 16
 # --truth-paf: PAF bytes per FASTQ byte that a batch's buffer is first sized for (measured 0.079 on configs[3]: profiles/truth_paf.md)
 PAF_SHARE = 0.1
+# --truth-sam: the same for a batch's SAM records (measured 1.43 on configs[3]: profiles/truth_sam.md)
+SAM_SHARE = 1.5
 E_SCRATCH, E_OUTPUT, E_NOFRAG = -3, -4, -5
 STAGE_NAMES = ('plan', 'build', 'mutate', 'scan', 'final', 'emit', 'align1', 'qscore')
 # kernel classes of brx_last_kernel_stats (include/brx.h: BRX_KERN_*), with the names a rocprofv3 kernel trace shows
@@ -292,6 +294,8 @@ def bind_library(lib):
     lib.brx_emit_paf.restype = ctypes.c_int
     lib.brx_emit_paf.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t),
                                  ctypes.c_void_p]
+    lib.brx_emit_sam.restype = ctypes.c_int
+    lib.brx_emit_sam.argtypes = lib.brx_emit_paf.argtypes
     lib.brx_last_mutate_passes.restype = ctypes.c_uint32
     lib.brx_last_mutate_passes.argtypes = [ctypes.c_void_p]
     lib.brx_last_final_launches.restype = ctypes.c_uint32
@@ -536,14 +540,22 @@ class HipEngine(EngineBase):
         """Truth alignments (PAF text, include/brx.h brx_emit_paf) of the last simulate_batch(_device) of this engine, which had
         `n_reads` reads: (device uint8 tensor of the records in read order, numpy uint64 offsets of each read's records, n_reads + 1
         entries).  The tensor is a fresh one: the engine may take its next batch at once."""
+        return self._emit_truth(self.lib.brx_emit_paf, PAF_SHARE, n_reads)
+
+    def emit_sam_device(self, n_reads):
+        """The same truth as SAM records (include/brx.h brx_emit_sam; no header), with emit_paf_device's arguments and results.
+        Both may be called for one batch, in either order."""
+        return self._emit_truth(self.lib.brx_emit_sam, SAM_SHARE, n_reads)
+
+    def _emit_truth(self, emit, share, n_reads):
+        """brx_emit_paf / brx_emit_sam into a buffer first sized as `share` of the expected FASTQ bytes; one retry on E_OUTPUT."""
         torch = self.torch
         off = torch.zeros(n_reads + 1, dtype=torch.int64, device=self.device)
-        cap = int(n_reads * PAF_SHARE * self.expected_record_bytes()) + (1 << 16)
+        cap = int(n_reads * share * self.expected_record_bytes()) + (1 << 16)
         for _ in range(2):
             out = torch.empty(cap, dtype=torch.uint8, device=self.device)
             got = ctypes.c_size_t(0)
-            rc = self.lib.brx_emit_paf(self.ctx, ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(off.data_ptr()),
-                                       ctypes.byref(got), self._stream())
+            rc = emit(self.ctx, ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(off.data_ptr()), ctypes.byref(got), self._stream())
             if rc != E_OUTPUT:
                 break
             cap = int(self.lib.brx_output_needed(self.ctx)) + 64

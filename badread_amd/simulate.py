@@ -34,7 +34,7 @@ import time
 import numpy as np
 
 from . import settings
-from .engine import PAF_SHARE, RS_BAND, RS_NOFRAG, RS_QMISS, RS_TOO_MANY_SEGS, SimParams
+from .engine import PAF_SHARE, SAM_SHARE, RS_BAND, RS_NOFRAG, RS_QMISS, RS_TOO_MANY_SEGS, SimParams
 from .error_model import ErrorModel
 from .fragment_lengths import FragmentLengths
 from .identities import Identities
@@ -283,6 +283,12 @@ class Shard(object):
         """One uint32 of every rank, as a list of ints in rank order."""
         return [int(x[0]) for x in self.gather_words(np.array([v], dtype=np.uint32), [1] * self.world)]
 
+    def gather_word64(self, v):
+        """One uint64 of every rank, as two words each: a byte count that may pass 2^32 (a super-batch's SAM records)."""
+        v = int(v)
+        parts = self.gather_words(np.array([v & 0xFFFFFFFF, v >> 32], dtype=np.uint32), [2] * self.world)
+        return [int(x[0]) | (int(x[1]) << 32) for x in parts]
+
     def collect_bytes(self, mine, sizes, staging):
         """Record bytes to rank 0, point to point: rank r > 0 sends its `sizes[r]` bytes (a device tensor over RCCL /
         xGMI in production, a CPU tensor over gloo in the tests) and rank 0 receives them in rank order into `staging`.
@@ -354,12 +360,14 @@ def kept_bytes(stats, first, base, last, n_mine):
     return keep, (int(stats['rec_off'][keep - 1] + stats['rec_len'][keep - 1]) if keep else 0)
 
 
-def expected_out_bytes(engine, n_reads, mean_length, truth_paf):
-    """Bytes a batch of `n_reads` reads is expected to leave on the device (with --truth-paf its PAF text too): by the engine's estimate
-    from its parameters, or at 2.1 B per base + 400 per read for an engine without one (None: its parameters are not set yet)."""
+def expected_out_bytes(engine, n_reads, mean_length, truth_paf, truth_sam=False):
+    """Bytes a batch of `n_reads` reads is expected to leave on the device (with --truth-paf its PAF text, with --truth-sam its SAM records
+    too): by the engine's estimate from its parameters, or at 2.1 B per base + 400 per read for an engine without one (None: its parameters
+    are not set yet)."""
     per_read = engine.expected_record_bytes() if hasattr(engine, 'expected_record_bytes') else 2.1 * mean_length + 400.0
     out_bytes = int(n_reads * per_read)
-    return int(out_bytes * (1.0 + PAF_SHARE)) if truth_paf else out_bytes
+    share = (PAF_SHARE if truth_paf else 0.0) + (SAM_SHARE if truth_sam else 0.0)
+    return int(out_bytes * (1.0 + share)) if share else out_bytes
 
 
 def driver_reserve_bytes():
@@ -509,7 +517,7 @@ class _ArenaPrefetch(object):
             pass
 
     @staticmethod
-    def for_job(engine, target_size, mean_length, error_rate, in_flight, world, truth_paf=False):
+    def for_job(engine, target_size, mean_length, error_rate, in_flight, world, truth_paf=False, truth_sam=False):
         """Arenas for the batches in flight of THIS job on THIS device, or None (not a GPU engine, a job of one small batch,
         BRX_ARENA_PREFETCH=0).  How many: what the job will use and the free memory holds (engines_for_memory, no arena mapped yet)."""
         # Measured (profiles/r05i_arena_prefetch.json, r05k_*; DESIGN.md has the figures): the read loop then runs undisturbed, 18.8-19.0 s for
@@ -522,7 +530,7 @@ class _ArenaPrefetch(object):
         if first_batch < 4096:
             return None                                  # a small job: one arena, sized by presize
         nbytes = engine.arena_bytes(first_batch, mean_length, error_rate) if hasattr(engine, 'arena_bytes') else arena_estimate(first_batch, mean_length, error_rate)
-        out_bytes = expected_out_bytes(None, first_batch, mean_length, truth_paf)        # the engine's parameters are not set yet
+        out_bytes = expected_out_bytes(None, first_batch, mean_length, truth_paf, truth_sam)        # the engine's parameters are not set yet
         batches = -(-int(target_size) // max(int(first_batch * mean_length * max(world, 1)), 1))
         free, _ = engine.torch.cuda.mem_get_info(engine.device)
         n = engines_for_memory(free, max(1, min(int(in_flight), batches)), nbytes, 0, out_bytes, driver_reserve_bytes())
@@ -545,9 +553,10 @@ class _BatchPool(object):
     bytes device-to-device out of the engine's buffer when the batch is done (2 GB at HBM speed: ~1 ms) and gives the engine back at once; `depth` =
     in_flight + 2 batches may be outstanding, the surplus holding only their bytes."""
 
-    def __init__(self, engine, in_flight, arenas=None, device_gzip=False, truth_paf=False):
+    def __init__(self, engine, in_flight, arenas=None, device_gzip=False, truth_paf=False, truth_sam=False):
         self.arenas = arenas
         self.truth_paf = bool(truth_paf)                 # --truth-paf: every batch's truth alignments, made by its worker beside its FASTQ
+        self.truth_sam = bool(truth_sam)                 # --truth-sam: the same as SAM records
         # --gzip-device: the worker of a batch that the stop rule cannot cut (submit(..., pack=True)) packs ITS batch on ITS engine's stream and hands
         # over the gzip members; the consumer packs only the job's last batches (every batch there: 10.4 s of configs[4]'s read loop against 6.0 s)
         self.device_gzip = bool(device_gzip)
@@ -623,7 +632,7 @@ class _BatchPool(object):
         return self.pool.submit(self._work, seed, first, n_mine, pack)
 
     def _work(self, seed, first, n_mine, pack):
-        """One batch on the next free engine, on a worker thread: (FASTQ bytes, stats, (text bytes, gzip members) or None, PAF or None)."""
+        """One batch on the next free engine, on a worker thread: (FASTQ bytes, stats, (text bytes, gzip members) or None, PAF or None, SAM or None)."""
         import torch
         t_q = time.perf_counter()
         i = self.free.get()
@@ -633,16 +642,18 @@ class _BatchPool(object):
         try:
             stream, eng = self.streams[i], self.engines[i]
             if n_mine == 0:
-                return torch.zeros(0, dtype=torch.uint8), np.zeros(0, dtype=eng.stats_dtype), None, None
+                return torch.zeros(0, dtype=torch.uint8), np.zeros(0, dtype=eng.stats_dtype), None, None, None
             if not self.on_gpu:
                 out, stats = eng.simulate_batch(seed, first, n_mine, allow_nofrag=True)
                 paf = eng.emit_paf_device(n_mine) if self.truth_paf else None
-                return torch.from_numpy(np.ascontiguousarray(out).copy()), stats.copy(), None, paf
+                sam = eng.emit_sam_device(n_mine) if self.truth_sam else None
+                return torch.from_numpy(np.ascontiguousarray(out).copy()), stats.copy(), None, paf, sam
             torch.cuda.set_device(eng.device)
             with torch.cuda.stream(stream):
                 out, stats = eng.simulate_batch_device(seed, first, n_mine, allow_nofrag=True)
                 # the truth alignments read what the batch left in the engine's arena: same job, same stream, before the engine is free
                 paf = eng.emit_paf_device(n_mine) if self.truth_paf else None
+                sam = eng.emit_sam_device(n_mine) if self.truth_sam else None
                 stats = stats.copy()
                 packed = None
                 if pack and self.device_gzip and len(stats) and hasattr(eng, 'gzip_device'):
@@ -654,7 +665,7 @@ class _BatchPool(object):
                         packed = (nbytes, eng.gzip_device(out[:nbytes], blocks))      # a new tensor, made on this batch's stream
                 out = self._copy_of(torch, out) if packed is None else None   # the engine's buffer is free again; the copy runs on this batch's stream ...
                 stream.synchronize()                     # ... and is complete before the engine is handed to the next batch
-                return out, stats, packed, paf
+                return out, stats, packed, paf, sam
         finally:
             with self.lock:
                 self.job_seconds += time.perf_counter() - t_job
@@ -672,7 +683,8 @@ class _BatchPool(object):
 
 
 def run_batches(engine, seed, target_size, mean_length, write, output, shard=None, max_batch=None, in_flight=1, device_gzip=False,
-                local_write=None, local_parts=None, expected_error=None, arenas=None, truth_paf=False, paf_write=None):
+                local_write=None, local_parts=None, expected_error=None, arenas=None, truth_paf=False, paf_write=None,
+                truth_sam=False, sam_write=None):
     """
     The `while total_size < target_size` loop (simulate.py:63-86) over super-batches of read indices.
     `write(bytes_like)` receives the FASTQ bytes in read order on rank 0 only.  Returns (read count, total bases).
@@ -698,11 +710,14 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
     read as the FASTQ.  `paf_write` receives them in read order: on rank 0, over the same point-to-point exchange as the
     FASTQ, or with local_write on every rank, its own reads' records (those of its own FASTQ file, in that file's order).
 
+    truth_sam / sam_write (--truth-sam): the same for the reads' SAM records (engine.emit_sam_device), through a ring of their
+    own.  The @ lines of the file are the caller's (sam_header).
+
     A sink that fails on one rank of a multi-rank run (a full disk, a closed pipe) is reported in the same exchange -- one
     word per rank -- so that every rank leaves the loop at the same batch instead of waiting in a collective.
     """
     run = _Run(engine, seed, target_size, mean_length, write, output, shard or Shard(), max_batch or DEFAULT_MAX_BATCH, in_flight,
-               device_gzip, local_write, local_parts, expected_error, arenas, truth_paf, paf_write)
+               device_gzip, local_write, local_parts, expected_error, arenas, truth_paf, paf_write, truth_sam, sam_write)
     run_batches.last_timing = run.timing
     run.size_pipeline()
     run.open_rings()
@@ -724,17 +739,18 @@ class _Run(object):
     (Shard.gather_words, collect_bytes) and every pool.submit comes at a point that depends only on consumed totals: the ranks stay in step."""
 
     def __init__(self, engine, seed, target_size, mean_length, write, output, shard, max_batch, in_flight, device_gzip,
-                 local_write, local_parts, expected_error, arenas, truth_paf, paf_write):
+                 local_write, local_parts, expected_error, arenas, truth_paf, paf_write, truth_sam=False, sam_write=None):
         import torch
         self.torch = torch
         self.engine, self.seed, self.target_size, self.write, self.output, self.shard = engine, seed, target_size, write, output, shard
         self.max_batch, self.in_flight, self.device_gzip, self.expected_error, self.arenas = max_batch, in_flight, device_gzip, expected_error, arenas
         self.local_write, self.local_parts, self.truth_paf, self.paf_write = local_write, local_parts, truth_paf, paf_write
+        self.truth_sam, self.sam_write = truth_sam, sam_write
         self.count = self.total = self.next_read = 0
         self.expected_mean = float(mean_length)
         self.pending = collections.deque()          # _Pending, in index order
         self.fatal, self.bad_read, self.sink_failed_on = False, None, None
-        self.pool = self.ring = self.paf_ring = self.gz_engine = None
+        self.pool = self.ring = self.paf_ring = self.sam_ring = self.gz_engine = None
         if shard.rank == 0:
             print_progress(0, 0, target_size, output)
         self.timing = collections.Counter()         # seconds of the consumer thread per activity (bench.py --d2h)
@@ -751,7 +767,7 @@ class _Run(object):
                 engine.adopt_scratch(first_arena)
             else:                                    # by the job's identity law, if given: arenas for Q30 reads are half those of 95 % reads
                 engine.presize(first_batch, self.expected_mean, self.expected_error)
-            out_bytes = expected_out_bytes(engine, first_batch, self.expected_mean, self.truth_paf)
+            out_bytes = expected_out_bytes(engine, first_batch, self.expected_mean, self.truth_paf, self.truth_sam)
         asked = fit = max(1, int(self.in_flight))
         if first_arena is not None:
             fit = min(fit, arenas.count)             # decided when the arenas were requested, by the same rule, from the memory that was free then
@@ -761,16 +777,18 @@ class _Run(object):
             fit = min(shard.gather_word(fit))
         if fit < asked and shard.rank == 0:
             print(f'  {fit} of the {asked} batches in flight asked for fit into the free device memory', file=self.output)
-        self.pool = _BatchPool(engine, fit, arenas, device_gzip=self.device_gzip, truth_paf=self.truth_paf)
+        self.pool = _BatchPool(engine, fit, arenas, device_gzip=self.device_gzip, truth_paf=self.truth_paf, truth_sam=self.truth_sam)
         self.timing['create_engines'] = time.perf_counter() - self.t_job
 
     def open_rings(self):
-        """A ring for the FASTQ bytes (rank 0, or every rank with local_write), one of its own for the PAF text, the consumer's gzip engine."""
+        """A ring for the FASTQ bytes (rank 0, or every rank with local_write), one of its own for the PAF text and for the SAM records, the consumer's gzip engine."""
         pinned, defer = self.pool.on_gpu, self.shard.world > 1
         if self.local_write is not None or self.shard.rank == 0:
             self.ring = _HostRing(self.torch, pinned, self.local_write if self.local_write is not None else self.write, defer)
         if self.truth_paf and self.paf_write is not None:
             self.paf_ring = _HostRing(self.torch, pinned, self.paf_write, defer)
+        if self.truth_sam and self.sam_write is not None:
+            self.sam_ring = _HostRing(self.torch, pinned, self.sam_write, defer)
         if self.device_gzip:
             if not hasattr(self.engine, 'gzip_device'):
                 sys.exit('Error: --gzip-device needs the GPU engine')
@@ -799,13 +817,13 @@ class _Run(object):
     def consume(self, batch):
         """The next super-batch in index order: wait, exchange, decide, pack, account, refill, ship.  False: the loop ends here."""
         timing, shard, t0 = self.timing, self.shard, time.perf_counter()
-        out, stats, prepacked, paf = batch.future.result()
+        out, stats, prepacked, paf, sam = batch.future.result()
         timing['wait_for_batch'] += time.perf_counter() - t0
         timing['batches'] += 1
         allw = exchange_words(stats)
-        if shard.world > 1:                         # every rank's words in read order, and one more of each rank: "my sink has failed" (FASTQ's or PAF's)
+        if shard.world > 1:                         # every rank's words in read order, and one more of each rank: "my sink has failed" (FASTQ's, PAF's or SAM's)
             per_rank = [Shard(r, shard.world).slice_of(batch.base, batch.n_super)[1] for r in range(shard.world)]
-            failed_here = any(x is not None and x.error is not None for x in (self.ring, self.paf_ring))
+            failed_here = any(x is not None and x.error is not None for x in (self.ring, self.paf_ring, self.sam_ring))
             parts = shard.gather_words(np.append(allw, np.uint32(1 if failed_here else 0)), [c + 1 for c in per_rank])
             failed = [r for r, part in enumerate(parts) if part[-1]]
             if failed:                              # every rank leaves here, at the same batch
@@ -838,6 +856,11 @@ class _Run(object):
                 paf_sizes = shard.gather_word(paf_bytes)
                 assert paf_bytes < 2 ** 32
             self.ship(self.paf_ring, paf[0] if paf is not None else None, paf_bytes, paf_sizes)
+        if self.truth_sam:                          # and their SAM records: a super-batch's may pass 2^32 bytes on a rank
+            sam_bytes, sam_sizes = int(sam[1][keep]) if sam is not None else 0, None
+            if shard.world > 1 and not local:
+                sam_sizes = shard.gather_word64(sam_bytes)
+            self.ship(self.sam_ring, sam[0] if sam is not None else None, sam_bytes, sam_sizes)
         timing['copy_out'] += time.perf_counter() - t0
         if shard.rank == 0:
             print_progress(self.count, self.total, self.target_size, self.output)
@@ -901,8 +924,9 @@ class _Run(object):
             self.ring.flush(reraise=not quiet and not self.ring.defer_errors)
             timing['sink'] = self.ring.sink_seconds
             timing['ring_alloc'] = self.ring.alloc_seconds
-        if self.paf_ring is not None:
-            self.paf_ring.flush(reraise=not quiet and not self.paf_ring.defer_errors)
+        for ring in (self.paf_ring, self.sam_ring):
+            if ring is not None:
+                ring.flush(reraise=not quiet and not ring.defer_errors)
         timing['flush'] = time.perf_counter() - t0
         timing['retries'] = sum(getattr(e, 'retries', 0) for e in pool.engines if e is not None)
         timing['device_batch_seconds_avg'] = pool.job_seconds / max(pool.job_count, 1.0)
@@ -916,7 +940,7 @@ class _Run(object):
 
     def raise_outcome(self):
         """The ways out other than a count: this rank's own sink, another rank's sink, no fragment, a read beyond the GPU path's limits."""
-        for ring in (self.ring, self.paf_ring):      # this rank's own sink, then its own PAF file
+        for ring in (self.ring, self.paf_ring, self.sam_ring):      # this rank's own sink, then its own PAF and SAM files
             if ring is not None and ring.error is not None and (self.sink_failed_on is not None or ring.defer_errors):
                 raise ring.error
         if self.sink_failed_on is not None:
@@ -972,8 +996,9 @@ class _PartsLog(object):
 
 class _Outputs(object):
     """Where a rank's bytes go (open_outputs): `write` to rank 0's stdout (through --gzip's sink if asked for); with --output-shards
-    `local_write` and `local_parts`, this rank's own file and parts log; with --truth-paf `paf_write`.  None where not in use."""
-    local_write = local_parts = paf_write = None
+    `local_write` and `local_parts`, this rank's own file and parts log; with --truth-paf `paf_write`, with --truth-sam `sam_write`.  None
+    where not in use."""
+    local_write = local_parts = paf_write = sam_write = None
 
     def __init__(self, sink):
         self.sink, self.files = sink, []
@@ -993,7 +1018,7 @@ class _Outputs(object):
             f.close()
 
 
-def open_outputs(args, shard, engine, stdout):
+def open_outputs(args, shard, engine, stdout, pref=None):
     """The sinks of one job.  Exits where the options exclude each other or, agreed between the ranks, where a rank cannot open its files."""
     sink = stdout if stdout is not None else getattr(sys.stdout, 'buffer', None)
     gzip_level = getattr(args, 'gzip_level', None)
@@ -1047,7 +1072,28 @@ def open_outputs(args, shard, engine, stdout):
             paf_file = open(f'{truth_paf}.{shard.rank}' if prefix else truth_paf, 'wb')
             outs.files.append(paf_file)
             outs.paf_write = paf_file.write
+    # --truth-sam PATH: the same as SAM (brx_emit_sam), the same files; each begins with the header, which depends on the reference alone
+    truth_sam = getattr(args, 'truth_sam', None)
+    if truth_sam:
+        if not hasattr(engine, 'emit_sam_device'):
+            shard.finish()
+            sys.exit('Error: --truth-sam needs the GPU engine')
+        if prefix or shard.rank == 0:
+            sam_file = open(f'{truth_sam}.{shard.rank}' if prefix else truth_sam, 'wb')
+            outs.files.append(sam_file)
+            sam_file.write(sam_header(pref))
+            outs.sam_write = sam_file.write
     return outs
+
+
+def sam_header(pref):
+    """The @ lines of a --truth-sam file: the contigs in reference order under the names the records use.  No CL: field and nothing
+    else of the run: the file does not depend on streams, batch sizes or ranks."""
+    from .version import __version__
+    lines = ['@HD\tVN:1.6\tSO:unsorted\tGO:query']
+    lines += [f'@SQ\tSN:{name}\tLN:{int(length)}' for name, length in zip(pref.names, pref.lengths)]
+    lines.append(f'@PG\tID:badread_amd\tPN:badread_amd\tVN:{__version__}')
+    return ('\n'.join(lines) + '\n').encode()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1084,7 +1130,7 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
     # the job's arenas from now on, beside everything below (models, tables, the first batch): _ArenaPrefetch
     arenas = _ArenaPrefetch.for_job(engine, get_target_size(pref.n_bases, args.quantity), float(args.mean_frag_length),
                                     expected_error_rate(identities), getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, shard.world,
-                                    truth_paf=bool(getattr(args, 'truth_paf', None)))
+                                    truth_paf=bool(getattr(args, 'truth_paf', None)), truth_sam=bool(getattr(args, 'truth_sam', None)))
     # a model file that is not in the cache is aligned (align_kmers, error_model.py:179-229) on THIS engine
     error_model = ErrorModel(args.error_model, quiet, aligner=lambda qs, ts: engine.align_batch(qs, ts)[0])
     qscore_model = QScoreModel(args.qscore_model, quiet)
@@ -1104,13 +1150,14 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
     engine.set_params(sim_params_from_args(args, frag_lengths, identities, start_rate, start_amount,
                                            end_rate, end_amount))
     mark('tables_on_device')
-    outs = open_outputs(args, shard, engine, stdout)
+    outs = open_outputs(args, shard, engine, stdout, pref)
     try:
         try:
             result = run_batches(engine, seed, target_size, float(args.mean_frag_length), outs.write, quiet, shard,
                                  in_flight=getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, device_gzip=bool(getattr(args, 'gzip_device', False)),
                                  local_write=outs.local_write, local_parts=outs.local_parts, expected_error=expected_error_rate(identities),
-                                 arenas=arenas, truth_paf=bool(getattr(args, 'truth_paf', None)), paf_write=outs.paf_write)
+                                 arenas=arenas, truth_paf=bool(getattr(args, 'truth_paf', None)), paf_write=outs.paf_write,
+                                 truth_sam=bool(getattr(args, 'truth_sam', None)), sam_write=outs.sam_write)
         finally:
             outs.close()
     except (SystemExit, OSError):

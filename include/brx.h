@@ -359,6 +359,16 @@ int brx_gzip_device(brx_ctx *ctx, const void *d_in, size_t n_bytes, const uint64
  * whose read bases are all in the FASTQ read, trimmed to its first and last =/X column (README: --truth-paf). */
 int brx_emit_paf(brx_ctx *ctx, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream);
 
+/* The same truth as SAM records (no header: the @HD/@SQ/@PG lines are the host's), under brx_emit_paf's contract: the reads
+ * of the LAST brx_simulate_batch on ctx, BRX_E_STATE where there is none, BRX_E_OUTPUT + brx_output_needed(), d_read_off,
+ * synchronous.  Both may be called for one batch, in either order.  One line per PAF record, in PAF order: FLAG 16 for '-',
+ * 2048 on all but the primary (tp:A:P); POS = tstart + 1, MAPQ 60; CIGAR = the record's cg:Z: between clips (S on the
+ * primary, H on the others); SEQ / QUAL = the whole read on the primary, the record's slice on the others, reverse-
+ * complemented (brx_reference.comp on the codes) / reversed for '-'; NM:i: and AS:i:, and on the primary CO:Z: with the
+ * FASTQ header line after the name.  A read with a FASTQ record and no PAF record gets one unmapped line (FLAG 4, with
+ * CO:Z:), a read without a FASTQ record none (README: --truth-sam). */
+int brx_emit_sam(brx_ctx *ctx, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
