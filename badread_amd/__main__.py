@@ -93,6 +93,10 @@ SIMULATE_OPTIONS = [
                                   'record, the whole read with SEQ, QUAL and the FASTQ header (CO:Z:) on the primary line, the '
                                   'record\'s slice on the supplementary ones, one unmapped line for a read with no record; can be '
                                   'combined with --truth-paf; with --output-shards every rank writes PATH.<rank>')),
+        ('--truth-bam', dict(type=str, default=None, dest='truth_bam', metavar='PATH',
+                             help='Also write the same true alignments to PATH as BAM (BGZF-compressed on the GPU): the header '
+                                  'and the records of --truth-sam, in the same order, unsorted; can be combined with --truth-paf '
+                                  'and --truth-sam; with --output-shards every rank writes PATH.<rank>, a complete BAM file')),
         ('--gpu-streams', dict(type=int, default=None, dest='gpu_streams',
                                help='Device batches in flight per GPU, each on its own HIP stream (default: 6)')),
     ]),
@@ -170,7 +174,7 @@ def check_simulate_args(args):
     """Validate and derive the fields simulate() reads (mean_frag_length, identity triple, glitch_*)."""
     if not pathlib.Path(args.reference).is_file():
         sys.exit(f'Error: {args.reference} is not a file')
-    for flag in ('truth_paf', 'truth_sam'):
+    for flag in ('truth_paf', 'truth_sam', 'truth_bam'):
         path = getattr(args, flag, None)
         if path is not None and not pathlib.Path(path).resolve().parent.is_dir():
             sys.exit(f'Error: the directory of --{flag.replace("_", "-")} {path} does not exist')

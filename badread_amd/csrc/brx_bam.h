@@ -1,0 +1,220 @@
+/*
+ * brx_bam.h -- truth alignments of a simulate batch as BAM records (brx_emit_bam; SAM spec v1 section 4.2).  Included once by
+ * brx_hip.hip after brx_sam.h.
+ *
+ * One record per line of brx_emit_sam, in the same order, with the same fields: the walk, the two sweeps and the choice of the
+ * primary are brx_paf.h's, the read's bases and the comment are found as brx_sam.h finds them.  All integers little-endian,
+ * nothing aligned (the name is 37 bytes: the CIGAR words start at an odd offset), so every store is a byte store.
+ *
+ *   block_size refID pos l_read_name=37 mapq bin n_cigar_op flag l_seq next_refID=-1 next_pos=-1 tlen=0 name\0
+ *   cigar (len << 4 | op, MIDNSH = 0..5)   seq (two bases per byte, '=ACMGRSVTWYHKDBN')   qual (FASTQ character - 33)
+ *   NM AS [CO:Z:comment\0] [CG:B:I]         (integers in the smallest type, htslib's rule)
+ *
+ * A record with more than max_ops CIGAR operations, clips included, takes the long form of section 4.2.2: the CIGAR field holds
+ * l_seq S and reflen N, the real operations follow as the last tag CG:B:I; bin comes from the real reflen either way.
+ *
+ * As in brx_sam.h the primary is known only when the sizing walk ends: k_bam_size sizes every record as supplementary and keeps
+ * what the best one adds as the primary (whole-read SEQ and QUAL, CO).  The operation count is the same for both (S and H clips),
+ * so the choice of the long form does not depend on it.  k_bam_size reads no sequence byte.  k_bam_write: one wave per read; lane 0
+ * writes the fixed fields, the clips and the tags, the wave places one CIGAR word per run, packs 128 bases into 64 bytes per
+ * step and copies 64 qualities per step -- consecutive lanes store consecutive bytes; on '-' records the loads run backwards.
+ */
+#ifndef BRX_BAM_H
+#define BRX_BAM_H
+
+#define BRX_BAM_CIGAR_AT 73u           /* block_size + 32 bytes of fixed fields + the name and its NUL */
+#define BRX_BAM_UNMAPPED_BIN 4680u     /* reg2bin(-1, 0) */
+enum { BAM_OP_M = 0, BAM_OP_I = 1, BAM_OP_D = 2, BAM_OP_N = 3, BAM_OP_S = 4, BAM_OP_H = 5 };
+
+template <class B> __device__ void put_le(B &b, uint64_t v, int bytes) { for (int i = 0; i < bytes; ++i) b.put((uint8_t)(v >> (8 * i))); }
+
+/* an integer tag in the smallest type that holds it: C S I from 0 up, c s i below */
+template <class B>
+__device__ void bam_tag_int(B &b, char t0, char t1, int64_t v) {
+    b.put((uint8_t)t0); b.put((uint8_t)t1);
+    if (v >= 0) { const int n = v <= 255 ? 1 : v <= 65535 ? 2 : 4; b.put((uint8_t)(n == 1 ? 'C' : n == 2 ? 'S' : 'I')); put_le(b, (uint64_t)v, n); }
+    else { const int n = v >= -128 ? 1 : v >= -32768 ? 2 : 4; b.put((uint8_t)(n == 1 ? 'c' : n == 2 ? 's' : 'i')); put_le(b, (uint64_t)v, n); }
+}
+template <class B> __device__ void bam_tags(B &b, uint32_t nm, int64_t as) { bam_tag_int(b, 'N', 'M', (int64_t)nm); bam_tag_int(b, 'A', 'S', as); }
+
+/* the spec's reg2bin (section 5.3) of [beg, end), as the 16 bits the field holds */
+__device__ __forceinline__ uint32_t bam_reg2bin(uint32_t beg, uint32_t end) {
+    --end;
+    if (beg >> 14 == end >> 14) return (((1u << 15) - 1u) / 7u + (beg >> 14)) & 0xFFFFu;
+    if (beg >> 17 == end >> 17) return ((1u << 12) - 1u) / 7u + (beg >> 17);
+    if (beg >> 20 == end >> 20) return ((1u << 9) - 1u) / 7u + (beg >> 20);
+    if (beg >> 23 == end >> 23) return ((1u << 6) - 1u) / 7u + (beg >> 23);
+    if (beg >> 26 == end >> 26) return ((1u << 3) - 1u) / 7u + (beg >> 26);
+    return 0u;
+}
+
+/* block_size .. tlen, the name and its NUL: BRX_BAM_CIGAR_AT bytes */
+template <class B>
+__device__ void bam_fixed(B &b, const BrxDev &d, uint64_t read, uint32_t block_size, uint32_t ref_id, uint32_t pos, uint32_t mapq, uint32_t bin,
+                          uint32_t n_cigar, uint32_t flag, uint32_t l_seq) {
+    put_le(b, block_size, 4); put_le(b, ref_id, 4); put_le(b, pos, 4);
+    b.put((uint8_t)(BRX_SAM_NAME + 1u)); b.put((uint8_t)mapq); put_le(b, bin, 2); put_le(b, n_cigar, 2); put_le(b, flag, 2); put_le(b, l_seq, 4);
+    put_le(b, 0xFFFFFFFFu, 4); put_le(b, 0xFFFFFFFFu, 4); put_le(b, 0u, 4);
+    put_uuid(b, d, read); b.put(0);
+}
+
+/* code -> nibble of '=ACMGRSVTWYHKDBN' (case-insensitive, anything else 15), sixteen nibbles in a word: forward, and through comp[] */
+struct BamNib { uint64_t fwd, rev; };
+__device__ __forceinline__ uint32_t bam_nibble_of(uint8_t ch) {
+    const char *set = "=ACMGRSVTWYHKDBN";
+    if (ch >= 'a' && ch <= 'z') ch = (uint8_t)(ch - 'a' + 'A');
+    for (uint32_t i = 0; i < 16; ++i) if ((uint8_t)set[i] == ch) return i;
+    return 15u;
+}
+/* Every lane calls it: lane c < 16 looks up code c, the wave sums the disjoint nibbles. */
+__device__ BamNib bam_nibbles(const BrxDev &d) {
+    const uint32_t lane = (uint32_t)lane_id(), c = lane & 15u, sh = 4u * (c & 7u);
+    const uint32_t f = bam_nibble_of(d.ref.sym[c]) << sh, r = bam_nibble_of(d.ref.sym[d.ref.comp[c] & 15u]) << sh;
+    const bool lo = lane < 8, hi = lane >= 8 && lane < 16;
+    BamNib T;
+    T.fwd = (uint64_t)wave_sum(lo ? f : 0u) | ((uint64_t)wave_sum(hi ? f : 0u) << 32);
+    T.rev = (uint64_t)wave_sum(lo ? r : 0u) | ((uint64_t)wave_sum(hi ? r : 0u) << 32);
+    return T;
+}
+
+/* SEQ and QUAL of the read's bases [lo, hi), reversed and complemented for a '-' record.  Every lane calls it. */
+__device__ void bam_bases(const BamNib &T, const SamRead &M, uint8_t *seq, uint8_t *qual, uint32_t lo, uint32_t hi, bool minus) {
+    const uint32_t lane = (uint32_t)lane_id(), len = hi - lo, packed = (len + 1u) / 2u;
+    const uint64_t tab = minus ? T.rev : T.fwd;
+    for (uint32_t x = lane; x < packed; x += 64) {
+        const uint32_t i0 = 2u * x, i1 = i0 + 1u;
+        const uint32_t n0 = (uint32_t)(tab >> (4u * (M.seq[minus ? hi - 1u - i0 : lo + i0] & 15u))) & 15u;
+        const uint32_t n1 = i1 < len ? (uint32_t)(tab >> (4u * (M.seq[minus ? hi - 1u - i1 : lo + i1] & 15u))) & 15u : 0u;
+        seq[x] = (uint8_t)((n0 << 4) | n1);
+    }
+    for (uint32_t x = lane; x < len; x += 64) qual[x] = (uint8_t)(M.qual[minus ? hi - 1u - x : lo + x] - 33u);
+}
+
+/* Sweep 2 of a record, binary: the lane whose column ends run i stores that run's word at ops[i] ('-' records: at ops[runs - 1 - i]),
+   byte by byte.  The runs are paf_cigar's. */
+__device__ void bam_cigar(const PafRead &R, const PafRec &q, uint8_t *ops, uint32_t runs, bool minus) {
+    const int lane = lane_id();
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint32_t done = 0, run_start = q.c0;
+    for (uint32_t b = q.c0; b <= q.c1; b += 64) {
+        const uint32_t c = b + lane;
+        const bool in = c <= q.c1;
+        const uint32_t op = in ? R.ops[c] : 0u;
+        const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
+        const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
+        const bool rs = in && (c == q.c0 || paf_cls(prev) != paf_cls(op));
+        const bool re = in && (c == q.c1 || paf_cls(next) != paf_cls(op));
+        const uint64_t rmask = __ballot(rs), emask = __ballot(re);
+        const uint64_t mine = rmask & (below | (1ull << lane));
+        const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
+        if (re) {
+            const uint32_t i = done + (uint32_t)__popcll(emask & below), cl = paf_cls(op);
+            const uint32_t word = ((c - s0 + 1u) << 4) | (cl == 0 ? (uint32_t)BAM_OP_M : cl == 2 ? (uint32_t)BAM_OP_I : (uint32_t)BAM_OP_D);
+            uint8_t *p = ops + 4ull * (minus ? runs - 1u - i : i);
+            p[0] = (uint8_t)word; p[1] = (uint8_t)(word >> 8); p[2] = (uint8_t)(word >> 16); p[3] = (uint8_t)(word >> 24);
+        }
+        done += (uint32_t)__popcll(emask);
+        if (rmask) run_start = b + (uint32_t)paf_top(rmask);
+    }
+}
+
+template <class S> __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q);
+struct BamCount {
+    static constexpr bool write = false; uint8_t *out; SamRead M; uint32_t max_ops, surplus; BamNib T;
+    __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { bam_record(*this, d, R, q); }
+};
+struct BamWrite {
+    static constexpr bool write = true; uint8_t *out; SamRead M; uint32_t max_ops; BamNib T;
+    __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { bam_record(*this, d, R, q); }
+};
+__device__ __forceinline__ void sink_surplus(BamCount &k, uint32_t v) { k.surplus = v; }
+__device__ __forceinline__ void sink_surplus(BamWrite &, uint32_t) {}
+
+__device__ __forceinline__ uint32_t bam_bases_bytes(uint32_t l_seq) { return (l_seq + 1u) / 2u + l_seq; }       /* SEQ and QUAL */
+
+/* One record of the read as a BAM record: sized (as a supplementary one; the primary's surplus goes with the best AS), or
+   written.  Every lane calls it (wave-uniform arguments). */
+template <class S>
+__device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q) {
+    const PafShape sh = paf_shape(R, q);
+    const uint32_t nm = sh.cnt[1] + sh.cnt[2] + sh.cnt[3];
+    const int64_t as = (int64_t)sh.cnt[0] - (int64_t)nm;
+    const uint32_t qcols = sh.cnt[0] + sh.cnt[1] + sh.cnt[2], tspan = sh.cnt[0] + sh.cnt[1] + sh.cnt[3];
+    const bool minus = ((q.key0 >> 32) & 1u) != 0;
+    const uint32_t L = R.seq_len, qs = q.r0 - R.start_trim, qe = qs + qcols;
+    const uint32_t left = minus ? L - qe : qs, right = minus ? qs : L - qe;
+    const bool primary = S::write && R.n_rec == R.best;
+    const bool top = paf_rank(R, as);
+    const uint32_t n_ops = sh.runs + (left ? 1u : 0u) + (right ? 1u : 0u);
+    const bool lng = n_ops > sink.max_ops;
+    const uint32_t n_cigar = lng ? 2u : n_ops;
+    const uint32_t comment = sam_comment(sink);
+    const uint32_t bases = primary ? L : qcols;
+    CountSink tc; tc.n = 0; bam_tags(tc, nm, as);
+    const uint32_t seq_at = BRX_BAM_CIGAR_AT + 4u * n_cigar, qual_at = seq_at + (bases + 1u) / 2u, tag_at = qual_at + bases;
+    const uint32_t cg_at = tag_at + tc.n + (primary ? 4u + comment : 0u);                       /* CO Z comment NUL */
+    const uint32_t bytes = cg_at + (lng ? 8u + 4u * n_ops : 0u);                                 /* CG B I count, the words */
+    if (S::write) {
+        uint8_t *o = sink.out + R.at;
+        uint8_t *ops = o + (lng ? cg_at + 8u : BRX_BAM_CIGAR_AT);
+        if (lane_id() == 0) {
+            const uint32_t cs = (uint32_t)(q.key0 >> 32), contig = cs >> 1, p0 = (uint32_t)q.key0;
+            const uint32_t ts = minus ? d.ref.d_contigs[contig].length - p0 - tspan : p0;
+            const uint32_t clip = primary ? (uint32_t)BAM_OP_S : (uint32_t)BAM_OP_H;
+            ByteSink h; h.p = o; h.n = 0;
+            bam_fixed(h, d, R.read, bytes - 4u, contig, ts, 60u, bam_reg2bin(ts, ts + tspan), n_cigar, (minus ? 16u : 0u) | (primary ? 0u : 2048u), bases);
+            if (lng) { put_le(h, (bases << 4) | BAM_OP_S, 4); put_le(h, (tspan << 4) | BAM_OP_N, 4); }
+            if (left) { ByteSink c; c.p = ops; c.n = 0; put_le(c, (left << 4) | clip, 4); }
+            if (right) { ByteSink c; c.p = ops + 4ull * (n_ops - 1u); c.n = 0; put_le(c, (right << 4) | clip, 4); }
+            ByteSink t; t.p = o + tag_at; t.n = 0;
+            bam_tags(t, nm, as);
+            if (primary) { t.put('C'); t.put('O'); t.put('Z'); put_comment(t, d, *sink.M.s, sink.M.pieces); t.put(0); }
+            if (lng) { t.put('C'); t.put('G'); t.put('B'); t.put('I'); put_le(t, n_ops, 4); }
+        }
+        bam_cigar(R, q, ops + (left ? 4u : 0u), sh.runs, minus);
+        bam_bases(sink.T, sink.M, o + seq_at, o + qual_at, primary ? 0u : qs, primary ? L : qe, minus);
+    } else if (top) {
+        /* the same record as the primary: SEQ and QUAL are the whole read, CO:Z:; the operations stay as many (S for H) */
+        sink_surplus(sink, bam_bases_bytes(L) - bam_bases_bytes(qcols) + 4u + comment);
+    }
+    R.at += bytes;
+}
+
+/* bytes of the unmapped record of a read of L bases: the fixed part, SEQ, QUAL, CO:Z: with the comment and its NUL */
+__device__ __forceinline__ uint32_t bam_unmapped_bytes(uint32_t L, uint32_t comment) { return BRX_BAM_CIGAR_AT + bam_bases_bytes(L) + 4u + comment; }
+
+/* bytes and primary record (BRX_SAM_UNMAPPED: none) of every read */
+__global__ void __launch_bounds__(64) k_bam_size(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t max_ops, uint32_t *len, uint32_t *best) {
+    const uint32_t r = blockIdx.x;
+    const RS s = rs[r];
+    PafRead R; R.at = 0; R.best = 0; R.top = 0; R.n_rec = 0;
+    BamCount k_; k_.out = nullptr; k_.surplus = 0; k_.max_ops = max_ops; k_.M = sam_of(s, nullptr, arena); k_.T.fwd = k_.T.rev = 0;
+    if (paf_has_records(s)) paf_read(k_, d, s, r, segs, arena, R);
+    uint32_t bytes = (uint32_t)R.at + k_.surplus, top = R.top;
+    if (R.n_rec == 0) { top = BRX_SAM_UNMAPPED; bytes = s.rec_len ? bam_unmapped_bytes(s.seq_len, sam_comment(k_)) : 0u; }
+    if (lane_id() == 0) { len[r] = bytes; best[r] = top; }
+}
+
+__global__ void __launch_bounds__(64) k_bam_write(BrxDev d, const RS *rs, const PSeg *segs, const PPiece *pieces, const uint8_t *arena, uint32_t max_ops,
+                                                   const uint64_t *off, const uint32_t *best, uint8_t *out) {
+    const uint32_t r = blockIdx.x;
+    const RS s = rs[r];
+    if (s.rec_len == 0) return;
+    BamWrite w; w.out = out; w.max_ops = max_ops; w.M = sam_of(s, pieces, arena); w.T = bam_nibbles(d);
+    if (best[r] != BRX_SAM_UNMAPPED) {
+        PafRead R; R.at = off[r]; R.best = best[r];
+        paf_read(w, d, s, r, segs, arena, R);
+        return;
+    }
+    uint8_t *o = out + off[r];
+    const uint32_t L = s.seq_len, qual_at = BRX_BAM_CIGAR_AT + (L + 1u) / 2u;
+    if (lane_id() == 0) {
+        ByteSink h; h.p = o; h.n = 0;
+        bam_fixed(h, d, d.first_read + r, bam_unmapped_bytes(L, sam_comment(w)) - 4u, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, BRX_BAM_UNMAPPED_BIN, 0u, 4u, L);
+        ByteSink t; t.p = o + qual_at + L; t.n = 0;
+        t.put('C'); t.put('O'); t.put('Z'); put_comment(t, d, s, pieces); t.put(0);
+    }
+    bam_bases(w.T, w.M, o + BRX_BAM_CIGAR_AT, o + qual_at, 0u, L, false);
+}
+
+#endif /* BRX_BAM_H */

@@ -22,6 +22,11 @@
  *               atomic OR for the two it shares with its neighbours -- end-of-block code, CRC-32 and length
  *
  * Memory-bound byte work (three reads of the input, one write of ~0.42 of it); no MFMA, no LDS tiling beyond the tables.
+ *
+ * The BGZF flavour (template argument; brx_bgzf_device, the blocks of a BAM file: SAM spec section 4.1) writes the same members
+ * behind an 18-byte header -- FLG.FEXTRA, XLEN 6, the subfield 'B' 'C' 2 0 and BSIZE = the member's size - 1 -- over fixed
+ * blocks of BRX_BGZF_BLOCK input bytes: with codes of at most 15 bits such a member needs at most 61 607 bytes, below the
+ * format's 65 536 for any input, so there is no stored-block fallback.
  */
 #ifndef BRX_GZIP_DEV_H
 #define BRX_GZIP_DEV_H
@@ -38,6 +43,9 @@ struct BrxGzConst { uint32_t x2n[32]; };     /* x^(2^k) mod P, reflected: x2n[0]
 
 /* member bytes a block of `len` input bytes can need at most (15-bit codes) */
 __host__ __device__ inline uint64_t brx_gz_member_bound(uint64_t len) { return 10 + (BRX_GZ_HDR_BITS + 15ull * (len + 1) + 7) / 8 + 8; }
+/* bytes before the deflate stream, input bytes of a block when the caller gives none */
+template <bool BGZF> struct BrxGzFlavour { static constexpr uint32_t hdr = BGZF ? 18u : 10u, block = BGZF ? BRX_BGZF_BLOCK : BRX_GZ_BLOCK; };
+static_assert(18 + (BRX_GZ_HDR_BITS + 15 * (BRX_BGZF_BLOCK + 1) + 7) / 8 + 8 <= 65536, "a BGZF block holds at most 64 KB");
 
 /* (a * b) mod P over GF(2), reflected representation (bit 31 = x^0) */
 __host__ __device__ inline uint32_t brx_gz_mulmod(uint32_t a, uint32_t b) {
@@ -64,12 +72,13 @@ __device__ __forceinline__ uint32_t brx_gz_rev(uint32_t code, uint32_t len) {   
     return r;
 }
 
-/* block b covers input bytes [blk_off[b], blk_off[b + 1]) -- or 64 KB pieces of [0, n) when blk_off is null */
-__device__ __forceinline__ void brx_gz_block(const uint64_t *blk_off, uint64_t n, uint32_t b, uint64_t *base, uint32_t *len) {
+/* block b covers input bytes [blk_off[b], blk_off[b + 1]) -- or pieces of `piece` bytes (64 KB; BGZF: 32 KB) of [0, n) when blk_off is null */
+__device__ __forceinline__ void brx_gz_block(const uint64_t *blk_off, uint64_t n, uint32_t b, uint32_t piece, uint64_t *base, uint32_t *len) {
     if (blk_off) { *base = blk_off[b]; *len = (uint32_t)(blk_off[b + 1] - blk_off[b]); }
-    else { *base = (uint64_t)b * BRX_GZ_BLOCK; *len = (uint32_t)(n - *base < BRX_GZ_BLOCK ? n - *base : BRX_GZ_BLOCK); }
+    else { *base = (uint64_t)b * piece; *len = (uint32_t)(n - *base < piece ? n - *base : piece); }
 }
 
+template <bool BGZF>
 __global__ void __launch_bounds__(64) k_gz_plan(const uint8_t *__restrict__ in, uint64_t n, const uint64_t *__restrict__ blk_off, uint32_t n_blocks, BrxGzConst K,
                                                 uint32_t *__restrict__ tabs, uint32_t *__restrict__ offs, uint32_t *__restrict__ crcs,
                                                 uint32_t *__restrict__ sizes) {
@@ -80,7 +89,7 @@ __global__ void __launch_bounds__(64) k_gz_plan(const uint8_t *__restrict__ in, 
     const int lane = threadIdx.x & 63;
     for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
         uint64_t base; uint32_t len;
-        brx_gz_block(blk_off, n, b, &base, &len);
+        brx_gz_block(blk_off, n, b, BrxGzFlavour<BGZF>::block, &base, &len);
         const uint32_t chunk = (len + 63u) / 64u;                  /* bytes per lane */
         for (uint32_t s = lane; s < BRX_GZ_TAB; s += 64) { hist[s] = 0; lens[s] = 0; tab[s] = 0; }
         for (uint32_t s = lane; s < 256; s += 64) {
@@ -180,7 +189,9 @@ __global__ void __launch_bounds__(64) k_gz_plan(const uint8_t *__restrict__ in, 
         for (int k = 0; k < 6; ++k) {
             const uint32_t r_crc = (uint32_t)__shfl_down((int)crc, 1u << k, 64), r_len = (uint32_t)__shfl_down((int)sub_len, 1u << k, 64);
             if ((lane & ((2 << k) - 1)) == 0) {
-                const uint32_t op = (chunk == 1024u && r_len == (1024u << k)) ? K.x2n[(13 + k) & 31] : brx_gz_x2nmodp(K.x2n, r_len, 3);
+                /* a full block's chunks are 1024 bytes (BGZF: 512): x^(8 * chunk * 2^k) is a table entry */
+                constexpr uint32_t full = BrxGzFlavour<BGZF>::block / 64u, lg = BGZF ? 12u : 13u;
+                const uint32_t op = (chunk == full && r_len == (full << k)) ? K.x2n[(lg + k) & 31] : brx_gz_x2nmodp(K.x2n, r_len, 3);
                 crc = brx_gz_mulmod(op, crc) ^ r_crc;
                 sub_len += r_len;
             }
@@ -189,7 +200,7 @@ __global__ void __launch_bounds__(64) k_gz_plan(const uint8_t *__restrict__ in, 
         if (lane == 0) {
             offs[(uint64_t)b * BRX_GZ_OFFS + 64] = total_bits;
             crcs[b] = crc;
-            sizes[b] = 10u + (BRX_GZ_HDR_BITS + total_bits + (tab[256] >> 16) + 7u) / 8u + 8u;
+            sizes[b] = BrxGzFlavour<BGZF>::hdr + (BRX_GZ_HDR_BITS + total_bits + (tab[256] >> 16) + 7u) / 8u + 8u;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_s_waitcnt(0);
@@ -220,6 +231,7 @@ __device__ __forceinline__ void brx_gz_put(uint32_t *out32, uint64_t pos, uint32
     if (sh + nbits > 32u) atomicOr(&out32[w + 1], value >> (32u - sh));
 }
 
+template <bool BGZF>
 __global__ void __launch_bounds__(64) k_gz_pack(const uint8_t *__restrict__ in, uint64_t n, const uint64_t *__restrict__ blk_off, uint32_t n_blocks, uint8_t *__restrict__ out,
                                                 const uint64_t *__restrict__ member_off, const uint32_t *__restrict__ tabs,
                                                 const uint32_t *__restrict__ offs, const uint32_t *__restrict__ crcs) {
@@ -228,16 +240,17 @@ __global__ void __launch_bounds__(64) k_gz_pack(const uint8_t *__restrict__ in, 
     uint32_t *out32 = reinterpret_cast<uint32_t *>(out);
     for (uint32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
         uint64_t base; uint32_t len;
-        brx_gz_block(blk_off, n, b, &base, &len);
+        brx_gz_block(blk_off, n, b, BrxGzFlavour<BGZF>::block, &base, &len);
         const uint32_t chunk = (len + 63u) / 64u;
         const uint64_t mo = member_off[b], mend = member_off[b + 1];
         for (uint32_t s = lane; s < BRX_GZ_TAB; s += 64) tab[s] = tabs[(uint64_t)b * BRX_GZ_TAB + s];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_s_waitcnt(0);
-        const uint64_t bit0 = 8ull * (mo + 10ull);                     /* first bit of the deflate stream */
+        const uint64_t bit0 = 8ull * (mo + BrxGzFlavour<BGZF>::hdr);  /* first bit of the deflate stream */
         if (lane == 0) {
-            const uint8_t hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
-            for (int i = 0; i < 10; ++i) out[mo + (uint64_t)i] = hdr[i];
+            const uint32_t bsize = (uint32_t)(mend - mo) - 1u;         /* BGZF: the member's size - 1, at most 61 606 */
+            const uint8_t hdr[18] = {0x1f, 0x8b, 8, BGZF ? 4 : 0, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, (uint8_t)bsize, (uint8_t)(bsize >> 8)};
+            for (uint32_t i = 0; i < BrxGzFlavour<BGZF>::hdr; ++i) out[mo + (uint64_t)i] = hdr[i];
             brx_gz_put(out32, bit0, 1u | (2u << 1), 3);                /* BFINAL = 1, BTYPE = 2 (dynamic Huffman codes) */
             brx_gz_put(out32, bit0 + 3, 0u | (1u << 5) | (15u << 10), 14);     /* HLIT = 257 - 257, HDIST = 2 - 1, HCLEN = 19 - 4 */
             /* code lengths of the code-length alphabet, in the order 16 17 18 0 8 7 ...: 0 for the run-length symbols,

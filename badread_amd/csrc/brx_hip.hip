@@ -23,6 +23,7 @@
 #include "brx_finplan.h"
 #include "brx_paf.h"
 #include "brx_sam.h"
+#include "brx_bam.h"
 
 #define BRX_KEV_MAX 2048
 
@@ -1219,13 +1220,15 @@ extern "C" size_t brx_gzip_device_scratch(size_t n_bytes, uint32_t n_blocks) {
     const size_t nb = n_blocks ? n_blocks : (n_bytes + BRX_GZ_BLOCK - 1) / BRX_GZ_BLOCK;
     return nb * (size_t)(4 * BRX_GZ_TAB + 4 * BRX_GZ_OFFS + 8) + (nb + 1) * 8 + 1024;
 }
-extern "C" int brx_gzip_device(brx_ctx *c, const void *d_in, size_t n_bytes, const uint64_t *d_block_off, uint32_t n_blocks, void *d_out, size_t out_cap,
-                               void *d_scratch, size_t scratch_bytes, size_t *out_bytes, void *hip_stream) {
+/* gzip members (brx_gzip_device) or BGZF blocks (brx_bgzf_device: fixed blocks of BRX_BGZF_BLOCK bytes) of d_in */
+template <bool BGZF>
+static int gz_members(brx_ctx *c, const void *d_in, size_t n_bytes, const uint64_t *d_block_off, uint32_t n_blocks, void *d_out, size_t out_cap,
+                      void *d_scratch, size_t scratch_bytes, size_t *out_bytes, void *hip_stream) {
     if (!c || !out_bytes || (n_bytes && (!d_in || !d_out || !d_scratch)) || (d_block_off && !n_blocks)) return BRX_E_ARG;
     *out_bytes = 0;
     if (!n_bytes) return BRX_OK;
     if ((uintptr_t)d_out & 3u) return fail(c, BRX_E_ARG, "brx_gzip_device: the output buffer must be 4-byte aligned");
-    const uint32_t nb = d_block_off ? n_blocks : (uint32_t)((n_bytes + BRX_GZ_BLOCK - 1) / BRX_GZ_BLOCK);
+    const uint32_t nb = d_block_off ? n_blocks : (uint32_t)((n_bytes + BrxGzFlavour<BGZF>::block - 1) / BrxGzFlavour<BGZF>::block);
     if (scratch_bytes < brx_gzip_device_scratch(n_bytes, nb)) return fail(c, BRX_E_SCRATCH, "brx_gzip_device: scratch too small (%zu < %zu)", scratch_bytes, brx_gzip_device_scratch(n_bytes, nb));
     hipStream_t st = (hipStream_t)hip_stream;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1237,22 +1240,38 @@ extern "C" int brx_gzip_device(brx_ctx *c, const void *d_in, size_t n_bytes, con
     uint32_t *crcs = (uint32_t *)p; p += (size_t)nb * 4;
     uint32_t *sizes = (uint32_t *)p;
     const uint32_t grid = std::min<uint32_t>(nb, (uint32_t)c->n_cu * 8u);
-    hipLaunchKernelGGL(k_gz_plan, dim3(grid), dim3(64), 0, st, (const uint8_t *)d_in, (uint64_t)n_bytes, d_block_off, nb, K, tabs, offs, crcs, sizes);
+    hipLaunchKernelGGL((k_gz_plan<BGZF>), dim3(grid), dim3(64), 0, st, (const uint8_t *)d_in, (uint64_t)n_bytes, d_block_off, nb, K, tabs, offs, crcs, sizes);
     hipLaunchKernelGGL(k_gz_scan, dim3(1), dim3(64), 0, st, nb, sizes, member_off);
     uint64_t total = 0;
     HIPCHK(c, hipMemcpyAsync(&total, member_off + nb, 8, hipMemcpyDeviceToHost, st));
     { int rcw = wait_stream(c, st, "brx_gzip_device (plan)"); if (rcw) return rcw; }
     if (total + 8 > out_cap) { c->output_needed = (size_t)total + 8; return fail(c, BRX_E_OUTPUT, "brx_gzip_device: output buffer too small: need %llu bytes", (unsigned long long)total + 8); }
     HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)((total + 7) & ~(uint64_t)3), st));
-    hipLaunchKernelGGL(k_gz_pack, dim3(grid), dim3(64), 0, st, (const uint8_t *)d_in, (uint64_t)n_bytes, d_block_off, nb, (uint8_t *)d_out, member_off, tabs, offs, crcs);
+    hipLaunchKernelGGL((k_gz_pack<BGZF>), dim3(grid), dim3(64), 0, st, (const uint8_t *)d_in, (uint64_t)n_bytes, d_block_off, nb, (uint8_t *)d_out, member_off, tabs, offs, crcs);
     { int rcw = wait_stream(c, st, "brx_gzip_device (pack)"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
     *out_bytes = (size_t)total;
     return BRX_OK;
 }
+extern "C" int brx_gzip_device(brx_ctx *c, const void *d_in, size_t n_bytes, const uint64_t *d_block_off, uint32_t n_blocks, void *d_out, size_t out_cap,
+                               void *d_scratch, size_t scratch_bytes, size_t *out_bytes, void *hip_stream) {
+    return gz_members<false>(c, d_in, n_bytes, d_block_off, n_blocks, d_out, out_cap, d_scratch, scratch_bytes, out_bytes, hip_stream);
+}
+static uint32_t bgzf_blocks(size_t n_bytes) { return (uint32_t)((n_bytes + BRX_BGZF_BLOCK - 1) / BRX_BGZF_BLOCK); }
+extern "C" size_t brx_bgzf_device_bound(size_t n_bytes) {
+    const size_t nb = bgzf_blocks(n_bytes);
+    return nb * (18 + (BRX_GZ_HDR_BITS + 15 + 7) / 8 + 8) + (15 * n_bytes + 7) / 8 + nb + 16;
+}
+extern "C" size_t brx_bgzf_device_scratch(size_t n_bytes) { return brx_gzip_device_scratch(n_bytes, bgzf_blocks(n_bytes)); }
+extern "C" int brx_bgzf_device(brx_ctx *c, const void *d_in, size_t n_bytes, void *d_out, size_t out_cap, void *d_scratch, size_t scratch_bytes,
+                               size_t *out_bytes, void *hip_stream) {
+    if (n_bytes > (size_t)BRX_BGZF_BLOCK * 0xFFFFFFFFull) return c ? fail(c, BRX_E_ARG, "brx_bgzf_device: input too long") : BRX_E_ARG;
+    return gz_members<true>(c, d_in, n_bytes, nullptr, 0, d_out, out_cap, d_scratch, scratch_bytes, out_bytes, hip_stream);
+}
 
-/* ---- truth alignments of the last simulate batch: PAF text (brx_paf.h) or SAM records (brx_sam.h) ---- */
-static int emit_truth(brx_ctx *c, bool sam, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+/* ---- truth alignments of the last simulate batch: PAF text (brx_paf.h), SAM records (brx_sam.h) or BAM records (brx_bam.h) ---- */
+enum { TRUTH_PAF = 0, TRUTH_SAM = 1, TRUTH_BAM = 2 };
+static int emit_truth(brx_ctx *c, int kind, uint32_t max_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
     if (!c || !out_bytes) return BRX_E_ARG;
     *out_bytes = 0;
     if (!c->paf_valid) return fail(c, BRX_E_STATE, "no simulate batch on this context to emit truth alignments for");
@@ -1271,30 +1290,40 @@ static int emit_truth(brx_ctx *c, bool sam, uint8_t *d_out, size_t out_cap, uint
     uint32_t *len = (uint32_t *)(c->d_paf + len_at), *best = (uint32_t *)(c->d_paf + best_at);
     uint64_t *off = (uint64_t *)(c->d_paf + off_at);
     const uint8_t *arena = (const uint8_t *)c->scratch;
-    if (n && sam) hipLaunchKernelGGL(k_sam_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best);
+    const bool sam = kind == TRUTH_SAM, bam = kind == TRUTH_BAM;
+    if (n && bam) hipLaunchKernelGGL(k_bam_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, max_ops, len, best);
+    else if (n && sam) hipLaunchKernelGGL(k_sam_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best);
     else if (n) hipLaunchKernelGGL(k_paf_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best);
-    if (sam) hipLaunchKernelGGL(k_sam_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
+    if (sam || bam) hipLaunchKernelGGL(k_sam_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
     else hipLaunchKernelGGL(k_paf_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
-    { int rcw = wait_stream(c, st, sam ? "k_sam_size" : "k_paf_size"); if (rcw) return rcw; }
+    { int rcw = wait_stream(c, st, bam ? "k_bam_size" : sam ? "k_sam_size" : "k_paf_size"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
     const uint64_t total = ((const uint64_t *)(c->h_paf + off_at))[n];
     if (total > out_cap || (total && !d_out)) {
         c->output_needed = total;
         return fail(c, BRX_E_OUTPUT, "truth alignment buffer too small: need %llu bytes", (unsigned long long)total);
     }
-    if (n && total && sam) hipLaunchKernelGGL(k_sam_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf,
+    if (n && total && bam) hipLaunchKernelGGL(k_bam_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf,
+                                              max_ops, (const uint64_t *)off, (const uint32_t *)best, d_out);
+    else if (n && total && sam) hipLaunchKernelGGL(k_sam_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf,
                                               (const uint64_t *)off, (const uint32_t *)best, d_out);
     else if (n && total) hipLaunchKernelGGL(k_paf_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena,
                                             (const uint64_t *)off, (const uint32_t *)best, d_out);
     if (d_read_off) HIPCHK(c, hipMemcpyAsync(d_read_off, c->h_paf + off_at, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-    { int rcw = wait_stream(c, st, sam ? "k_sam_write" : "k_paf_write"); if (rcw) return rcw; }
+    { int rcw = wait_stream(c, st, bam ? "k_bam_write" : sam ? "k_sam_write" : "k_paf_write"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
     *out_bytes = (size_t)total;
     return BRX_OK;
 }
 extern "C" int brx_emit_paf(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return emit_truth(c, false, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+    return emit_truth(c, TRUTH_PAF, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
 }
 extern "C" int brx_emit_sam(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return emit_truth(c, true, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+    return emit_truth(c, TRUTH_SAM, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+}
+extern "C" int brx_emit_bam(brx_ctx *c, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+    if (!c || !out_bytes) return BRX_E_ARG;
+    if (max_cigar_ops == 0) max_cigar_ops = 65535;
+    if (max_cigar_ops < 2 || max_cigar_ops > 65535) return fail(c, BRX_E_ARG, "brx_emit_bam: max_cigar_ops %u (2..65535, or 0 for 65535)", max_cigar_ops);
+    return emit_truth(c, TRUTH_BAM, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
 }

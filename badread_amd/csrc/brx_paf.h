@@ -36,7 +36,7 @@ struct PafRead {                                                 /* what a recor
     uint32_t best;                   /* the primary record (writing sink: found by the sizing pass) */
     uint32_t n_rec, top, top_set; int64_t top_as; uint64_t at;      /* records so far, the first of the highest AS among them */
 };
-struct PafShape { uint32_t cnt[4], text; };                      /* a record's columns by op, the text length of its CIGAR */
+struct PafShape { uint32_t cnt[4], text, runs; };                /* a record's columns by op, the text length and the runs of its CIGAR */
 
 /* The sinks of the walk (paf_read): what is done with every record it closes.  brx_sam.h adds its own two. */
 template <class S> __device__ void paf_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q);
@@ -73,12 +73,12 @@ __device__ void paf_tags(B &b, uint32_t nm, int64_t as) {
 template <class B>
 __device__ void paf_tail(B &b, uint32_t nm, int64_t as) { paf_tags(b, nm, as); b.put('\n'); }
 
-/* Sweep 1 over the record [q.c0, q.c1]: op counts and the CIGAR's text length.  A lane whose column ends a run (the next column
+/* Sweep 1 over the record [q.c0, q.c1]: op counts, the CIGAR's text length and its number of runs.  A lane whose column ends a run (the next column
    is another class, or the record ends) owns that run's text: its decimal length and the letter.  Every lane calls it. */
 __device__ PafShape paf_shape(const PafRead &R, const PafRec &q) {
     const int lane = lane_id();
     const uint64_t below = (1ull << lane) - 1ull;
-    PafShape sh; sh.cnt[0] = sh.cnt[1] = sh.cnt[2] = sh.cnt[3] = 0; sh.text = 0;
+    PafShape sh; sh.cnt[0] = sh.cnt[1] = sh.cnt[2] = sh.cnt[3] = 0; sh.text = 0; sh.runs = 0;
     uint32_t run_start = q.c0;
     for (uint32_t b = q.c0; b <= q.c1; b += 64) {
         const uint32_t c = b + lane;
@@ -93,6 +93,7 @@ __device__ PafShape paf_shape(const PafRead &R, const PafRec &q) {
         const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
         const uint32_t t = re ? paf_digits(c - s0 + 1) + 1u : 0u;
         sh.text += wave_sum(t);
+        sh.runs += (uint32_t)__popcll(rmask);
         for (uint32_t o = 0; o < 4; ++o) sh.cnt[o] += (uint32_t)__popcll(__ballot(in && op == o));
         if (rmask) run_start = b + (uint32_t)paf_top(rmask);
     }

@@ -82,6 +82,8 @@ RS_NOFRAG, RS_TOO_MANY_SEGS, RS_BAND, RS_QMISS, RS_EMPTY = 1, 2, 4, 8, 16
 PAF_SHARE = 0.1
 # --truth-sam: the same for a batch's SAM records (measured 1.43 on configs[3]: profiles/truth_sam.md)
 SAM_SHARE = 1.5
+# --truth-bam: the same for a batch's BAM records before they are compressed (measured 1.14 on configs[3]: profiles/truth_bam.md)
+BAM_SHARE = 1.2
 E_SCRATCH, E_OUTPUT, E_NOFRAG = -3, -4, -5
 STAGE_NAMES = ('plan', 'build', 'mutate', 'scan', 'final', 'emit', 'align1', 'qscore')
 # kernel classes of brx_last_kernel_stats (include/brx.h: BRX_KERN_*), with the names a rocprofv3 kernel trace shows
@@ -296,6 +298,15 @@ def bind_library(lib):
                                  ctypes.c_void_p]
     lib.brx_emit_sam.restype = ctypes.c_int
     lib.brx_emit_sam.argtypes = lib.brx_emit_paf.argtypes
+    lib.brx_emit_bam.restype = ctypes.c_int
+    lib.brx_emit_bam.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + list(lib.brx_emit_paf.argtypes[1:])
+    lib.brx_bgzf_device_bound.restype = ctypes.c_size_t
+    lib.brx_bgzf_device_bound.argtypes = [ctypes.c_size_t]
+    lib.brx_bgzf_device_scratch.restype = ctypes.c_size_t
+    lib.brx_bgzf_device_scratch.argtypes = [ctypes.c_size_t]
+    lib.brx_bgzf_device.restype = ctypes.c_int
+    lib.brx_bgzf_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                    ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
     lib.brx_last_mutate_passes.restype = ctypes.c_uint32
     lib.brx_last_mutate_passes.argtypes = [ctypes.c_void_p]
     lib.brx_last_final_launches.restype = ctypes.c_uint32
@@ -547,8 +558,35 @@ class HipEngine(EngineBase):
         Both may be called for one batch, in either order."""
         return self._emit_truth(self.lib.brx_emit_sam, SAM_SHARE, n_reads)
 
+    def emit_bam_device(self, n_reads, max_cigar_ops=65535):
+        """The same truth as uncompressed BAM records (include/brx.h brx_emit_bam; no header), one per SAM line, with
+        emit_paf_device's arguments and results.  A record with more than `max_cigar_ops` CIGAR operations takes the CG:B:I form."""
+        emit = lambda ctx, *rest: self.lib.brx_emit_bam(ctx, int(max_cigar_ops), *rest)
+        return self._emit_truth(emit, BAM_SHARE, n_reads)
+
+    def bgzf_device(self, data):
+        """brx_bgzf_device: a uint8 tensor on this engine's device -> a uint8 tensor (same device) holding BGZF blocks of it, one per
+        32 KB of input.  No data, no block; the file's EOF block is the caller's (output.BGZF_EOF)."""
+        torch = self.torch
+        n = int(data.numel())
+        if n == 0:
+            return torch.zeros(0, dtype=torch.uint8, device=self.device)
+        step = lambda b: b if b <= (1 << 24) else -(-b // (1 << 26)) * (1 << 26)       # as gzip_device: capacities the allocator can reuse
+        scratch = torch.empty(step(int(self.lib.brx_bgzf_device_scratch(n)) + 8), dtype=torch.uint8, device=self.device)
+        cap = min(int(0.7 * n) + 200 * -(-n // 32768) + 4096, int(self.lib.brx_bgzf_device_bound(n)) + 8)
+        got = ctypes.c_size_t(0)
+        for _ in range(2):
+            out = torch.empty(step(cap), dtype=torch.uint8, device=self.device)
+            rc = self.lib.brx_bgzf_device(self.ctx, ctypes.c_void_p(data.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), out.numel(),
+                                          ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), ctypes.byref(got), self._stream())
+            if rc != E_OUTPUT:
+                break
+            cap = int(self.lib.brx_output_needed(self.ctx)) + 8
+        self._check(rc)
+        return out[:got.value]
+
     def _emit_truth(self, emit, share, n_reads):
-        """brx_emit_paf / brx_emit_sam into a buffer first sized as `share` of the expected FASTQ bytes; one retry on E_OUTPUT."""
+        """brx_emit_paf / brx_emit_sam / brx_emit_bam into a buffer first sized as `share` of the expected FASTQ bytes; one retry on E_OUTPUT."""
         torch = self.torch
         off = torch.zeros(n_reads + 1, dtype=torch.int64, device=self.device)
         cap = int(n_reads * share * self.expected_record_bytes()) + (1 << 16)

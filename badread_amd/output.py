@@ -3,9 +3,14 @@ Host output stage.  The reference prints FASTQ tex
 `| gzip` pipe -- one core of deflate behind a simulator that emits GB/s.  `GzipSink` compresses every batch of FASTQ
 bytes on all usable host cores through libbrx_host.so (csrc/brx_gzip.cpp: independent gzip members of 1 MB, which
 `gzip -d` and every gzip reader treat as one stream) before it reaches stdout; `--gzip LEVEL` on the command line.
+
+`bam_header`, `bgzf_host` and `BGZF_EOF` are the host's share of a --truth-bam file (SAM spec v1 section 4): the header
+block(s) and the end-of-file marker around the BGZF blocks that brx_bgzf_device makes of the records on the GPU.
 """
 import ctypes
 import os
+import struct
+import zlib
 
 import numpy as np
 
@@ -99,3 +104,45 @@ def fastq_blocks(rec_off, rec_len, seq_len, n_bytes):
         extra = [np.arange(a + MAX_BLOCK, b, MAX_BLOCK, dtype=np.int64) for a, b in zip(cuts[:-1][gaps > MAX_BLOCK], cuts[1:][gaps > MAX_BLOCK])]
         cuts = np.unique(np.concatenate([cuts] + extra))
     return cuts.astype(np.uint64)
+
+
+# ---------------------------------------------------------------------------------------------
+# --truth-bam: what the host writes around the records' BGZF blocks
+# ---------------------------------------------------------------------------------------------
+BGZF_MAX_INPUT = 0xff00   # input bytes per block written here (htslib's choice: any input then fits a 64 KB block, stored if need be)
+BGZF_EOF = bytes.fromhex('1f8b08040000000000ff0600424302001b0003000000000000000000')      # the empty block that ends a file
+MAX_BAM_CONTIG = 2 ** 31 - 1
+
+
+def bgzf_block(data, level=6):
+    """One BGZF block (a gzip member with the BC extra subfield: BSIZE = its size - 1) of at most BGZF_MAX_INPUT bytes."""
+    assert len(data) <= BGZF_MAX_INPUT
+    packer = zlib.compressobj(level, zlib.DEFLATED, -15)
+    body = packer.compress(data) + packer.flush()
+    if len(body) + 26 > 65536:                   # incompressible bytes: deflate's stored form is 5 bytes longer than the input
+        packer = zlib.compressobj(0, zlib.DEFLATED, -15)
+        body = packer.compress(data) + packer.flush()
+    head = struct.pack('<4BI2BH2BHH', 0x1f, 0x8b, 8, 4, 0, 0, 0xff, 6, ord('B'), ord('C'), 2, len(body) + 25)
+    return head + body + struct.pack('<II', zlib.crc32(data), len(data))
+
+
+def bgzf_host(data, level=6):
+    """`data` as BGZF blocks of at most BGZF_MAX_INPUT input bytes each, back to back; nothing for no data (and no EOF block)."""
+    data = bytes(data)
+    return b''.join(bgzf_block(data[at:at + BGZF_MAX_INPUT], level) for at in range(0, len(data), BGZF_MAX_INPUT))
+
+
+def bam_header(pref, text=None):
+    """The uncompressed header of a --truth-bam file: magic, the text of the SAM header (simulate.sam_header, unchanged), the
+    contigs in reference order.  ValueError for a contig BAM's 32-bit signed positions cannot address."""
+    if text is None:
+        from .simulate import sam_header
+        text = sam_header(pref)
+    long_ones = [str(n) for n, x in zip(pref.names, pref.lengths) if int(x) > MAX_BAM_CONTIG]
+    if long_ones:
+        raise ValueError(f'contig {long_ones[0]} is longer than {MAX_BAM_CONTIG} bases, the longest BAM can address')
+    parts = [b'BAM\1', struct.pack('<i', len(text)), text, struct.pack('<i', len(pref.names))]
+    for name, length in zip(pref.names, pref.lengths):
+        raw = str(name).encode() + b'\0'
+        parts += [struct.pack('<i', len(raw)), raw, struct.pack('<i', int(length))]
+    return b''.join(parts)

@@ -34,7 +34,7 @@ import time
 import numpy as np
 
 from . import settings
-from .engine import PAF_SHARE, SAM_SHARE, RS_BAND, RS_NOFRAG, RS_QMISS, RS_TOO_MANY_SEGS, SimParams
+from .engine import BAM_SHARE, PAF_SHARE, SAM_SHARE, RS_BAND, RS_NOFRAG, RS_QMISS, RS_TOO_MANY_SEGS, SimParams
 from .error_model import ErrorModel
 from .fragment_lengths import FragmentLengths
 from .identities import Identities
@@ -360,13 +360,13 @@ def kept_bytes(stats, first, base, last, n_mine):
     return keep, (int(stats['rec_off'][keep - 1] + stats['rec_len'][keep - 1]) if keep else 0)
 
 
-def expected_out_bytes(engine, n_reads, mean_length, truth_paf, truth_sam=False):
-    """Bytes a batch of `n_reads` reads is expected to leave on the device (with --truth-paf its PAF text, with --truth-sam its SAM records
-    too): by the engine's estimate from its parameters, or at 2.1 B per base + 400 per read for an engine without one (None: its parameters
+def expected_out_bytes(engine, n_reads, mean_length, truth_paf, truth_sam=False, truth_bam=False):
+    """Bytes a batch of `n_reads` reads is expected to leave on the device (with --truth-paf its PAF text, with --truth-sam its SAM records,
+    with --truth-bam its BAM records before they are compressed too): by the engine's estimate from its parameters, or at 2.1 B per base + 400 per read for an engine without one (None: its parameters
     are not set yet)."""
     per_read = engine.expected_record_bytes() if hasattr(engine, 'expected_record_bytes') else 2.1 * mean_length + 400.0
     out_bytes = int(n_reads * per_read)
-    share = (PAF_SHARE if truth_paf else 0.0) + (SAM_SHARE if truth_sam else 0.0)
+    share = (PAF_SHARE if truth_paf else 0.0) + (SAM_SHARE if truth_sam else 0.0) + (BAM_SHARE if truth_bam else 0.0)
     return int(out_bytes * (1.0 + share)) if share else out_bytes
 
 
@@ -517,7 +517,7 @@ class _ArenaPrefetch(object):
             pass
 
     @staticmethod
-    def for_job(engine, target_size, mean_length, error_rate, in_flight, world, truth_paf=False, truth_sam=False):
+    def for_job(engine, target_size, mean_length, error_rate, in_flight, world, truth_paf=False, truth_sam=False, truth_bam=False):
         """Arenas for the batches in flight of THIS job on THIS device, or None (not a GPU engine, a job of one small batch,
         BRX_ARENA_PREFETCH=0).  How many: what the job will use and the free memory holds (engines_for_memory, no arena mapped yet)."""
         # Measured (profiles/r05i_arena_prefetch.json, r05k_*; DESIGN.md has the figures): the read loop then runs undisturbed, 18.8-19.0 s for
@@ -530,7 +530,7 @@ class _ArenaPrefetch(object):
         if first_batch < 4096:
             return None                                  # a small job: one arena, sized by presize
         nbytes = engine.arena_bytes(first_batch, mean_length, error_rate) if hasattr(engine, 'arena_bytes') else arena_estimate(first_batch, mean_length, error_rate)
-        out_bytes = expected_out_bytes(None, first_batch, mean_length, truth_paf, truth_sam)        # the engine's parameters are not set yet
+        out_bytes = expected_out_bytes(None, first_batch, mean_length, truth_paf, truth_sam, truth_bam)        # the engine's parameters are not set yet
         batches = -(-int(target_size) // max(int(first_batch * mean_length * max(world, 1)), 1))
         free, _ = engine.torch.cuda.mem_get_info(engine.device)
         n = engines_for_memory(free, max(1, min(int(in_flight), batches)), nbytes, 0, out_bytes, driver_reserve_bytes())
@@ -553,10 +553,13 @@ class _BatchPool(object):
     bytes device-to-device out of the engine's buffer when the batch is done (2 GB at HBM speed: ~1 ms) and gives the engine back at once; `depth` =
     in_flight + 2 batches may be outstanding, the surplus holding only their bytes."""
 
-    def __init__(self, engine, in_flight, arenas=None, device_gzip=False, truth_paf=False, truth_sam=False):
+    def __init__(self, engine, in_flight, arenas=None, device_gzip=False, truth_paf=False, truth_sam=False, truth_bam=False):
         self.arenas = arenas
         self.truth_paf = bool(truth_paf)                 # --truth-paf: every batch's truth alignments, made by its worker beside its FASTQ
         self.truth_sam = bool(truth_sam)                 # --truth-sam: the same as SAM records
+        # --truth-bam: the same as BAM records, which the worker of a batch that the stop rule cannot cut (submit(..., pack=True)) also compresses
+        # whole into BGZF blocks on its engine's stream; any other batch's are compressed by the consumer, for the reads it keeps
+        self.truth_bam = bool(truth_bam)
         # --gzip-device: the worker of a batch that the stop rule cannot cut (submit(..., pack=True)) packs ITS batch on ITS engine's stream and hands
         # over the gzip members; the consumer packs only the job's last batches (every batch there: 10.4 s of configs[4]'s read loop against 6.0 s)
         self.device_gzip = bool(device_gzip)
@@ -632,7 +635,8 @@ class _BatchPool(object):
         return self.pool.submit(self._work, seed, first, n_mine, pack)
 
     def _work(self, seed, first, n_mine, pack):
-        """One batch on the next free engine, on a worker thread: (FASTQ bytes, stats, (text bytes, gzip members) or None, PAF or None, SAM or None)."""
+        """One batch on the next free engine, on a worker thread: (FASTQ bytes, stats, (text bytes, gzip members) or None, PAF or None, SAM or None,
+        BAM or None); BAM = (records or their BGZF blocks, read offsets into the records, whether these are the blocks)."""
         import torch
         t_q = time.perf_counter()
         i = self.free.get()
@@ -642,18 +646,20 @@ class _BatchPool(object):
         try:
             stream, eng = self.streams[i], self.engines[i]
             if n_mine == 0:
-                return torch.zeros(0, dtype=torch.uint8), np.zeros(0, dtype=eng.stats_dtype), None, None, None
+                return torch.zeros(0, dtype=torch.uint8), np.zeros(0, dtype=eng.stats_dtype), None, None, None, None
             if not self.on_gpu:
                 out, stats = eng.simulate_batch(seed, first, n_mine, allow_nofrag=True)
                 paf = eng.emit_paf_device(n_mine) if self.truth_paf else None
                 sam = eng.emit_sam_device(n_mine) if self.truth_sam else None
-                return torch.from_numpy(np.ascontiguousarray(out).copy()), stats.copy(), None, paf, sam
+                bam = self._bam_of(eng, n_mine, pack) if self.truth_bam else None
+                return torch.from_numpy(np.ascontiguousarray(out).copy()), stats.copy(), None, paf, sam, bam
             torch.cuda.set_device(eng.device)
             with torch.cuda.stream(stream):
                 out, stats = eng.simulate_batch_device(seed, first, n_mine, allow_nofrag=True)
                 # the truth alignments read what the batch left in the engine's arena: same job, same stream, before the engine is free
                 paf = eng.emit_paf_device(n_mine) if self.truth_paf else None
                 sam = eng.emit_sam_device(n_mine) if self.truth_sam else None
+                bam = self._bam_of(eng, n_mine, pack) if self.truth_bam else None
                 stats = stats.copy()
                 packed = None
                 if pack and self.device_gzip and len(stats) and hasattr(eng, 'gzip_device'):
@@ -665,12 +671,20 @@ class _BatchPool(object):
                         packed = (nbytes, eng.gzip_device(out[:nbytes], blocks))      # a new tensor, made on this batch's stream
                 out = self._copy_of(torch, out) if packed is None else None   # the engine's buffer is free again; the copy runs on this batch's stream ...
                 stream.synchronize()                     # ... and is complete before the engine is handed to the next batch
-                return out, stats, packed, paf, sam
+                return out, stats, packed, paf, sam, bam
         finally:
             with self.lock:
                 self.job_seconds += time.perf_counter() - t_job
                 self.job_count += 1
             self.free.put(i)
+
+    @staticmethod
+    def _bam_of(eng, n_mine, pack):
+        """The batch's BAM records and read offsets; with `pack` the records' BGZF blocks instead, made at once on the same stream."""
+        data, off = eng.emit_bam_device(n_mine)
+        if pack and int(data.numel()):
+            return eng.bgzf_device(data), off, True
+        return data, off, False
 
     def close(self):
         for th in self.makers[:self.started]:            # clones no batch asked for were never started
@@ -684,7 +698,7 @@ class _BatchPool(object):
 
 def run_batches(engine, seed, target_size, mean_length, write, output, shard=None, max_batch=None, in_flight=1, device_gzip=False,
                 local_write=None, local_parts=None, expected_error=None, arenas=None, truth_paf=False, paf_write=None,
-                truth_sam=False, sam_write=None):
+                truth_sam=False, sam_write=None, truth_bam=False, bam_write=None):
     """
     The `while total_size < target_size` loop (simulate.py:63-86) over super-batches of read indices.
     `write(bytes_like)` receives the FASTQ bytes in read order on rank 0 only.  Returns (read count, total bases).
@@ -713,11 +727,15 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
     truth_sam / sam_write (--truth-sam): the same for the reads' SAM records (engine.emit_sam_device), through a ring of their
     own.  The @ lines of the file are the caller's (sam_header).
 
+    truth_bam / bam_write (--truth-bam): the same records in BAM's binary form (engine.emit_bam_device), cut at the same read and then
+    compressed on the GPU into BGZF blocks (engine.bgzf_device); only the blocks cross to the host, through a ring of their own, and
+    between ranks.  A batch the stop rule cannot cut is compressed whole by its worker.  Header and EOF block are the caller's.
+
     A sink that fails on one rank of a multi-rank run (a full disk, a closed pipe) is reported in the same exchange -- one
     word per rank -- so that every rank leaves the loop at the same batch instead of waiting in a collective.
     """
     run = _Run(engine, seed, target_size, mean_length, write, output, shard or Shard(), max_batch or DEFAULT_MAX_BATCH, in_flight,
-               device_gzip, local_write, local_parts, expected_error, arenas, truth_paf, paf_write, truth_sam, sam_write)
+               device_gzip, local_write, local_parts, expected_error, arenas, truth_paf, paf_write, truth_sam, sam_write, truth_bam, bam_write)
     run_batches.last_timing = run.timing
     run.size_pipeline()
     run.open_rings()
@@ -739,18 +757,20 @@ class _Run(object):
     (Shard.gather_words, collect_bytes) and every pool.submit comes at a point that depends only on consumed totals: the ranks stay in step."""
 
     def __init__(self, engine, seed, target_size, mean_length, write, output, shard, max_batch, in_flight, device_gzip,
-                 local_write, local_parts, expected_error, arenas, truth_paf, paf_write, truth_sam=False, sam_write=None):
+                 local_write, local_parts, expected_error, arenas, truth_paf, paf_write, truth_sam=False, sam_write=None,
+                 truth_bam=False, bam_write=None):
         import torch
         self.torch = torch
         self.engine, self.seed, self.target_size, self.write, self.output, self.shard = engine, seed, target_size, write, output, shard
         self.max_batch, self.in_flight, self.device_gzip, self.expected_error, self.arenas = max_batch, in_flight, device_gzip, expected_error, arenas
         self.local_write, self.local_parts, self.truth_paf, self.paf_write = local_write, local_parts, truth_paf, paf_write
         self.truth_sam, self.sam_write = truth_sam, sam_write
+        self.truth_bam, self.bam_write = truth_bam, bam_write
         self.count = self.total = self.next_read = 0
         self.expected_mean = float(mean_length)
         self.pending = collections.deque()          # _Pending, in index order
         self.fatal, self.bad_read, self.sink_failed_on = False, None, None
-        self.pool = self.ring = self.paf_ring = self.sam_ring = self.gz_engine = None
+        self.pool = self.ring = self.paf_ring = self.sam_ring = self.bam_ring = self.gz_engine = None
         if shard.rank == 0:
             print_progress(0, 0, target_size, output)
         self.timing = collections.Counter()         # seconds of the consumer thread per activity (bench.py --d2h)
@@ -767,7 +787,7 @@ class _Run(object):
                 engine.adopt_scratch(first_arena)
             else:                                    # by the job's identity law, if given: arenas for Q30 reads are half those of 95 % reads
                 engine.presize(first_batch, self.expected_mean, self.expected_error)
-            out_bytes = expected_out_bytes(engine, first_batch, self.expected_mean, self.truth_paf, self.truth_sam)
+            out_bytes = expected_out_bytes(engine, first_batch, self.expected_mean, self.truth_paf, self.truth_sam, self.truth_bam)
         asked = fit = max(1, int(self.in_flight))
         if first_arena is not None:
             fit = min(fit, arenas.count)             # decided when the arenas were requested, by the same rule, from the memory that was free then
@@ -777,11 +797,13 @@ class _Run(object):
             fit = min(shard.gather_word(fit))
         if fit < asked and shard.rank == 0:
             print(f'  {fit} of the {asked} batches in flight asked for fit into the free device memory', file=self.output)
-        self.pool = _BatchPool(engine, fit, arenas, device_gzip=self.device_gzip, truth_paf=self.truth_paf, truth_sam=self.truth_sam)
+        self.pool = _BatchPool(engine, fit, arenas, device_gzip=self.device_gzip, truth_paf=self.truth_paf, truth_sam=self.truth_sam,
+                               truth_bam=self.truth_bam)
         self.timing['create_engines'] = time.perf_counter() - self.t_job
 
     def open_rings(self):
-        """A ring for the FASTQ bytes (rank 0, or every rank with local_write), one of its own for the PAF text and for the SAM records, the consumer's gzip engine."""
+        """A ring for the FASTQ bytes (rank 0, or every rank with local_write), one of its own for the PAF text, for the SAM records and for the
+        BAM blocks, the consumer's small engine for gzip members and BGZF blocks."""
         pinned, defer = self.pool.on_gpu, self.shard.world > 1
         if self.local_write is not None or self.shard.rank == 0:
             self.ring = _HostRing(self.torch, pinned, self.local_write if self.local_write is not None else self.write, defer)
@@ -789,9 +811,11 @@ class _Run(object):
             self.paf_ring = _HostRing(self.torch, pinned, self.paf_write, defer)
         if self.truth_sam and self.sam_write is not None:
             self.sam_ring = _HostRing(self.torch, pinned, self.sam_write, defer)
-        if self.device_gzip:
-            if not hasattr(self.engine, 'gzip_device'):
-                sys.exit('Error: --gzip-device needs the GPU engine')
+        if self.truth_bam and self.bam_write is not None:
+            self.bam_ring = _HostRing(self.torch, pinned, self.bam_write, defer)
+        if self.device_gzip and not hasattr(self.engine, 'gzip_device'):
+            sys.exit('Error: --gzip-device needs the GPU engine')
+        if self.device_gzip or self.truth_bam:
             self.gz_engine = self.engine.clone(1 << 20) if hasattr(self.engine, 'clone') else self.engine      # its own context: the others are busy
 
     def staging(self, nbytes):
@@ -810,20 +834,21 @@ class _Run(object):
             n_super = plan_batch(max(remaining, 1), self.expected_mean, self.shard.world, self.max_batch)
             first, n_mine = self.shard.slice_of(self.next_read, n_super)
             # --gzip-device: a batch with at least three batches' worth of bases still to come behind it is kept whole
-            pack = self.device_gzip and remaining > 4.0 * n_super * self.expected_mean
+            # (--truth-bam: the same batches' BAM records are compressed whole by their workers)
+            pack = (self.device_gzip or self.truth_bam) and remaining > 4.0 * n_super * self.expected_mean
             self.pending.append(_Pending(self.pool.submit(self.seed, first, n_mine, pack=pack), self.next_read, n_super, first, n_mine))
             self.next_read += n_super
 
     def consume(self, batch):
         """The next super-batch in index order: wait, exchange, decide, pack, account, refill, ship.  False: the loop ends here."""
         timing, shard, t0 = self.timing, self.shard, time.perf_counter()
-        out, stats, prepacked, paf, sam = batch.future.result()
+        out, stats, prepacked, paf, sam, bam = batch.future.result()
         timing['wait_for_batch'] += time.perf_counter() - t0
         timing['batches'] += 1
         allw = exchange_words(stats)
         if shard.world > 1:                         # every rank's words in read order, and one more of each rank: "my sink has failed" (FASTQ's, PAF's or SAM's)
             per_rank = [Shard(r, shard.world).slice_of(batch.base, batch.n_super)[1] for r in range(shard.world)]
-            failed_here = any(x is not None and x.error is not None for x in (self.ring, self.paf_ring, self.sam_ring))
+            failed_here = any(x is not None and x.error is not None for x in (self.ring, self.paf_ring, self.sam_ring, self.bam_ring))
             parts = shard.gather_words(np.append(allw, np.uint32(1 if failed_here else 0)), [c + 1 for c in per_rank])
             failed = [r for r, part in enumerate(parts) if part[-1]]
             if failed:                              # every rank leaves here, at the same batch
@@ -861,6 +886,12 @@ class _Run(object):
             if shard.world > 1 and not local:
                 sam_sizes = shard.gather_word64(sam_bytes)
             self.ship(self.sam_ring, sam[0] if sam is not None else None, sam_bytes, sam_sizes)
+        if self.truth_bam:                          # and their BAM records, as BGZF blocks: whole blocks of every rank, so rank 0 only concatenates
+            blocks = self.pack_bam(bam, keep)
+            bam_bytes, bam_sizes = int(blocks.numel()) if blocks is not None else 0, None
+            if shard.world > 1 and not local:
+                bam_sizes = shard.gather_word64(bam_bytes)
+            self.ship(self.bam_ring, blocks, bam_bytes, bam_sizes)
         timing['copy_out'] += time.perf_counter() - t0
         if shard.rank == 0:
             print_progress(self.count, self.total, self.target_size, self.output)
@@ -875,7 +906,7 @@ class _Run(object):
         if prepacked is not None:      # reads far longer than the job expected: unpack on the host, once
             text = gzip.decompress(bytes(prepacked[1].cpu().numpy()))
             out = self.torch.from_numpy(np.frombuffer(text, dtype=np.uint8).copy()).to(prepacked[1].device)
-        if self.gz_engine is not None and my_bytes:
+        if self.device_gzip and self.gz_engine is not None and my_bytes:
             from .output import fastq_blocks
             t0 = time.perf_counter()
             blocks = fastq_blocks(stats['rec_off'][:keep], stats['rec_len'][:keep], stats['seq_len'][:keep], my_bytes)
@@ -883,6 +914,25 @@ class _Run(object):
             my_bytes = int(out.numel())
             self.timing['device_gzip'] += time.perf_counter() - t0
         return out, my_bytes
+
+    def pack_bam(self, bam, keep):
+        """The BGZF blocks of the BAM records of this rank's first `keep` reads (None: no reads here).  A batch its worker compressed whole
+        leaves as it is; one the stop rule cut after all is unpacked on the host, once (a BGZF stream is a gzip stream), and like every
+        batch not compressed ahead its kept records are compressed here, on the consumer's small engine."""
+        if bam is None:
+            return None
+        data, off, packed = bam
+        raw = int(off[keep])
+        if packed and raw == int(off[-1]):
+            self.timing['bam_batches_packed_by_their_worker'] += 1
+            return data
+        if packed:
+            records = gzip.decompress(bytes(data.cpu().numpy()))
+            data = self.torch.from_numpy(np.frombuffer(records, dtype=np.uint8).copy()).to(data.device)
+        t0 = time.perf_counter()
+        blocks = self.gz_engine.bgzf_device(data[:raw])
+        self.timing['device_bgzf'] += time.perf_counter() - t0
+        return blocks
 
     def ship(self, ring, data, nbytes, sizes):
         """`nbytes` of `data` into this rank's own `ring` (sizes None), or every rank's `sizes` bytes point to point into rank 0's."""
@@ -924,7 +974,7 @@ class _Run(object):
             self.ring.flush(reraise=not quiet and not self.ring.defer_errors)
             timing['sink'] = self.ring.sink_seconds
             timing['ring_alloc'] = self.ring.alloc_seconds
-        for ring in (self.paf_ring, self.sam_ring):
+        for ring in (self.paf_ring, self.sam_ring, self.bam_ring):
             if ring is not None:
                 ring.flush(reraise=not quiet and not ring.defer_errors)
         timing['flush'] = time.perf_counter() - t0
@@ -940,7 +990,7 @@ class _Run(object):
 
     def raise_outcome(self):
         """The ways out other than a count: this rank's own sink, another rank's sink, no fragment, a read beyond the GPU path's limits."""
-        for ring in (self.ring, self.paf_ring, self.sam_ring):      # this rank's own sink, then its own PAF and SAM files
+        for ring in (self.ring, self.paf_ring, self.sam_ring, self.bam_ring):      # this rank's own sink, then its own PAF, SAM and BAM files
             if ring is not None and ring.error is not None and (self.sink_failed_on is not None or ring.defer_errors):
                 raise ring.error
         if self.sink_failed_on is not None:
@@ -996,12 +1046,12 @@ class _PartsLog(object):
 
 class _Outputs(object):
     """Where a rank's bytes go (open_outputs): `write` to rank 0's stdout (through --gzip's sink if asked for); with --output-shards
-    `local_write` and `local_parts`, this rank's own file and parts log; with --truth-paf `paf_write`, with --truth-sam `sam_write`.  None
-    where not in use."""
-    local_write = local_parts = paf_write = sam_write = None
+    `local_write` and `local_parts`, this rank's own file and parts log; with --truth-paf `paf_write`, with --truth-sam `sam_write`, with
+    --truth-bam `bam_write`.  None where not in use."""
+    local_write = local_parts = paf_write = sam_write = bam_write = None
 
     def __init__(self, sink):
-        self.sink, self.files = sink, []
+        self.sink, self.files, self.bam_files = sink, [], []
 
     def write(self, part):
         if self.sink is not None:
@@ -1014,6 +1064,10 @@ class _Outputs(object):
             self.sink.flush()
 
     def close(self):
+        from .output import BGZF_EOF
+        for f in self.bam_files:                # the block that tells a reader the file is whole
+            with contextlib.suppress(OSError):
+                f.write(BGZF_EOF)
         for f in self.files:
             f.close()
 
@@ -1083,6 +1137,24 @@ def open_outputs(args, shard, engine, stdout, pref=None):
             outs.files.append(sam_file)
             sam_file.write(sam_header(pref))
             outs.sam_write = sam_file.write
+    # --truth-bam PATH: the same header and records as BAM; the host writes the header's BGZF blocks and, on closing, the EOF block
+    truth_bam = getattr(args, 'truth_bam', None)
+    if truth_bam:
+        if not hasattr(engine, 'emit_bam_device'):
+            shard.finish()
+            sys.exit('Error: --truth-bam needs the GPU engine')
+        from .output import bam_header, bgzf_host
+        try:
+            header = bam_header(pref)
+        except ValueError as ex:               # every rank alike: it depends on the reference alone
+            shard.finish()
+            sys.exit(f'Error: --truth-bam: {ex}')
+        if prefix or shard.rank == 0:
+            bam_file = open(f'{truth_bam}.{shard.rank}' if prefix else truth_bam, 'wb')
+            outs.files.append(bam_file)
+            outs.bam_files.append(bam_file)
+            bam_file.write(bgzf_host(header))
+            outs.bam_write = bam_file.write
     return outs
 
 
@@ -1130,7 +1202,8 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
     # the job's arenas from now on, beside everything below (models, tables, the first batch): _ArenaPrefetch
     arenas = _ArenaPrefetch.for_job(engine, get_target_size(pref.n_bases, args.quantity), float(args.mean_frag_length),
                                     expected_error_rate(identities), getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, shard.world,
-                                    truth_paf=bool(getattr(args, 'truth_paf', None)), truth_sam=bool(getattr(args, 'truth_sam', None)))
+                                    truth_paf=bool(getattr(args, 'truth_paf', None)), truth_sam=bool(getattr(args, 'truth_sam', None)),
+                                    truth_bam=bool(getattr(args, 'truth_bam', None)))
     # a model file that is not in the cache is aligned (align_kmers, error_model.py:179-229) on THIS engine
     error_model = ErrorModel(args.error_model, quiet, aligner=lambda qs, ts: engine.align_batch(qs, ts)[0])
     qscore_model = QScoreModel(args.qscore_model, quiet)
@@ -1157,7 +1230,8 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
                                  in_flight=getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, device_gzip=bool(getattr(args, 'gzip_device', False)),
                                  local_write=outs.local_write, local_parts=outs.local_parts, expected_error=expected_error_rate(identities),
                                  arenas=arenas, truth_paf=bool(getattr(args, 'truth_paf', None)), paf_write=outs.paf_write,
-                                 truth_sam=bool(getattr(args, 'truth_sam', None)), sam_write=outs.sam_write)
+                                 truth_sam=bool(getattr(args, 'truth_sam', None)), sam_write=outs.sam_write,
+                                 truth_bam=bool(getattr(args, 'truth_bam', None)), bam_write=outs.bam_write)
         finally:
             outs.close()
     except (SystemExit, OSError):

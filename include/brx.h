@@ -369,6 +369,29 @@ int brx_emit_paf(brx_ctx *ctx, uint8_t *d_out, size_t out_cap, uint64_t *d_read_
  * CO:Z:), a read without a FASTQ record none (README: --truth-sam). */
 int brx_emit_sam(brx_ctx *ctx, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream);
 
+/* The same records as uncompressed BAM (SAM spec v1 section 4.2; no header, no BGZF), one per line of brx_emit_sam in the same
+ * order, under the same contract: BRX_E_STATE, BRX_E_OUTPUT + brx_output_needed() with nothing written, d_read_off, synchronous;
+ * callable before or after brx_emit_paf / brx_emit_sam, which stay byte-identical.  Little-endian, nothing aligned.  refID = the
+ * contig's index, pos = POS - 1, l_read_name 37, mapq 60, bin = reg2bin(pos, pos + reflen), next_refID / next_pos -1, tlen 0; an
+ * unmapped record has refID -1, pos -1, mapq 0, bin 4680, no CIGAR, flag 4.  SEQ in nibbles of '=ACMGRSVTWYHKDBN' (anything else
+ * 15), QUAL = character - 33.  Tags NM, AS (smallest integer type: C S I, below zero c s i), CO:Z: on primary and unmapped
+ * records.  A record with more than max_cigar_ops operations, clips included (0 = 65535; below 2 or above 65535: BRX_E_ARG),
+ * holds `l_seq S, reflen N` as its CIGAR and the real operations in a last tag CG:B:I (README: --truth-bam). */
+int brx_emit_bam(brx_ctx *ctx, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes,
+                 void *hip_stream);
+
+/* n_bytes of device memory as BGZF blocks (SAM spec v1 section 4.1) back to back, one per BRX_BGZF_BLOCK input bytes, the last
+ * one possibly shorter, none for no input: the members of brx_gzip_device (one dynamic Huffman code per block, no match search)
+ * behind the 18-byte BGZF header (FEXTRA, 'B' 'C', BSIZE = the block's size - 1).  A block needs at most 61 607 bytes, so every
+ * input fits the format's 64 KB without a stored block.  No EOF block: the caller ends its file with one.  Buffers as for
+ * brx_gzip_device: d_out of brx_bgzf_device_bound(n_bytes) bytes (4-byte aligned; less is tried first by the Python wrapper,
+ * BRX_E_OUTPUT + brx_output_needed() says what is missing), d_scratch of brx_bgzf_device_scratch(n_bytes).  Synchronous. */
+#define BRX_BGZF_BLOCK 32768u
+size_t brx_bgzf_device_bound(size_t n_bytes);
+size_t brx_bgzf_device_scratch(size_t n_bytes);
+int brx_bgzf_device(brx_ctx *ctx, const void *d_in, size_t n_bytes, void *d_out, size_t out_cap, void *d_scratch, size_t scratch_bytes,
+                    size_t *out_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
