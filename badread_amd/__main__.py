@@ -97,6 +97,10 @@ SIMULATE_OPTIONS = [
                              help='Also write the same true alignments to PATH as BAM (BGZF-compressed on the GPU): the header '
                                   'and the records of --truth-sam, in the same order, unsorted; can be combined with --truth-paf '
                                   'and --truth-sam; with --output-shards every rank writes PATH.<rank>, a complete BAM file')),
+        ('--truth-tags', dict(type=str, default=None, dest='truth_tags', metavar='LIST',
+                              help='Tags to add to the records of --truth-sam and --truth-bam, a comma-separated list of MD and SA: '
+                                   'MD:Z: (mismatched and deleted reference bases) on every mapped line, SA:Z: (the read\'s other '
+                                   'alignments) on every mapped line of a read with two or more')),
         ('--gpu-streams', dict(type=int, default=None, dest='gpu_streams',
                                help='Device batches in flight per GPU, each on its own HIP stream (default: 6)')),
     ]),
@@ -170,6 +174,21 @@ def _floats(text, count=None):
     return values
 
 
+TRUTH_TAGS = {'MD': 1, 'SA': 2}          # include/brx.h: BRX_TAG_MD, BRX_TAG_SA
+
+
+def truth_tags_mask(text, has_file):
+    """--truth-tags LIST as the bit mask simulate() reads (0 without the option)."""
+    if text is None:
+        return 0
+    parts = text.split(',')
+    if not all(x in TRUTH_TAGS for x in parts):
+        sys.exit('Error: --truth-tags must be a comma-separated list of MD and SA')
+    if not has_file:
+        sys.exit('Error: --truth-tags needs --truth-sam or --truth-bam')
+    return sum({TRUTH_TAGS[x] for x in parts})
+
+
 def check_simulate_args(args):
     """Validate and derive the fields simulate() reads (mean_frag_length, identity triple, glitch_*)."""
     if not pathlib.Path(args.reference).is_file():
@@ -178,6 +197,7 @@ def check_simulate_args(args):
         path = getattr(args, flag, None)
         if path is not None and not pathlib.Path(path).resolve().parent.is_dir():
             sys.exit(f'Error: the directory of --{flag.replace("_", "-")} {path} does not exist')
+    args.truth_tags = truth_tags_mask(getattr(args, 'truth_tags', None), getattr(args, 'truth_sam', None) or getattr(args, 'truth_bam', None))
     for value, names, flag in ((args.error_model, ERROR_MODEL_NAMES, '--error_model'),
                                (args.qscore_model, QSCORE_MODEL_NAMES, '--qscore_model')):
         if value.lower() not in names and not pathlib.Path(value).is_file():

@@ -8,7 +8,8 @@
  *
  *   block_size refID pos l_read_name=37 mapq bin n_cigar_op flag l_seq next_refID=-1 next_pos=-1 tlen=0 name\0
  *   cigar (len << 4 | op, MIDNSH = 0..5)   seq (two bases per byte, '=ACMGRSVTWYHKDBN')   qual (FASTQ character - 33)
- *   NM AS [CO:Z:comment\0] [CG:B:I]         (integers in the smallest type, htslib's rule)
+ *   NM AS [MD:Z:text\0] [SA:Z:text\0] [CO:Z:comment\0] [CG:B:I]     (integers in the smallest type, htslib's rule; MD and SA:
+ *                                            brx_emit_bam_tags, the texts of brx_sam.h's md_sweep and sa_write)
  *
  * A record with more than max_ops CIGAR operations, clips included, takes the long form of section 4.2.2: the CIGAR field holds
  * l_seq S and reflen N, the real operations follow as the last tag CG:B:I; bin comes from the real reflen either way.
@@ -119,16 +120,19 @@ __device__ void bam_cigar(const PafRead &R, const PafRec &q, uint8_t *ops, uint3
 }
 
 template <class S> __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q);
-struct BamCount {
-    static constexpr bool write = false; uint8_t *out; SamRead M; uint32_t max_ops, surplus; BamNib T;
+template <uint32_t TAGS> struct BamCount {
+    static constexpr bool write = false, need_f0 = (TAGS & BRX_TAG_MD) != 0; static constexpr uint32_t tags = TAGS;
+    uint8_t *out; SamRead M; uint32_t max_ops, surplus; BamNib T; SaRead A;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { bam_record(*this, d, R, q); }
 };
-struct BamWrite {
-    static constexpr bool write = true; uint8_t *out; SamRead M; uint32_t max_ops; BamNib T;
+template <uint32_t TAGS> struct BamWrite {
+    static constexpr bool write = true, need_f0 = (TAGS & BRX_TAG_MD) != 0; static constexpr uint32_t tags = TAGS;
+    uint8_t *out; SamRead M; uint32_t max_ops; BamNib T; SaRead A;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { bam_record(*this, d, R, q); }
 };
-__device__ __forceinline__ void sink_surplus(BamCount &k, uint32_t v) { k.surplus = v; }
-__device__ __forceinline__ void sink_surplus(BamWrite &, uint32_t) {}
+template <uint32_t TAGS> __device__ __forceinline__ void sink_surplus(BamCount<TAGS> &k, uint32_t v) { k.surplus = v; }
+template <uint32_t TAGS> __device__ __forceinline__ void sink_surplus(BamWrite<TAGS> &, uint32_t) {}
+#define BRX_BAM_ZTAG 4u                /* a Z tag around its text: two letters, 'Z' and the NUL */
 
 __device__ __forceinline__ uint32_t bam_bases_bytes(uint32_t l_seq) { return (l_seq + 1u) / 2u + l_seq; }       /* SEQ and QUAL */
 
@@ -143,8 +147,17 @@ __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
     const bool minus = ((q.key0 >> 32) & 1u) != 0;
     const uint32_t L = R.seq_len, qs = q.r0 - R.start_trim, qe = qs + qcols;
     const uint32_t left = minus ? L - qe : qs, right = minus ? qs : L - qe;
-    const bool primary = S::write && R.n_rec == R.best;
+    const uint32_t line = R.n_rec;
+    const bool primary = S::write && line == R.best;
     const bool top = paf_rank(R, as);
+    /* MD and SA as Z tags (a sized record counts no SA: k_bam_size adds the read's at the end) */
+    MdShape md; md.text = md.tail = 0;
+    uint32_t md_len = 0, sa_len = 0;
+    if (S::tags & BRX_TAG_MD) { md = md_sweep<false>(d, R, q, minus, nullptr, md); md_len = BRX_BAM_ZTAG + md.text; }
+    if (S::tags & BRX_TAG_SA) {
+        if (!S::write) sink.A.sum += sa_rec_of(d, R, q, sh).len;
+        else if (sink.A.n) sa_len = BRX_BAM_ZTAG + sink.A.sum - sink.A.tab[line].len;
+    }
     const uint32_t n_ops = sh.runs + (left ? 1u : 0u) + (right ? 1u : 0u);
     const bool lng = n_ops > sink.max_ops;
     const uint32_t n_cigar = lng ? 2u : n_ops;
@@ -152,7 +165,7 @@ __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
     const uint32_t bases = primary ? L : qcols;
     CountSink tc; tc.n = 0; bam_tags(tc, nm, as);
     const uint32_t seq_at = BRX_BAM_CIGAR_AT + 4u * n_cigar, qual_at = seq_at + (bases + 1u) / 2u, tag_at = qual_at + bases;
-    const uint32_t cg_at = tag_at + tc.n + (primary ? 4u + comment : 0u);                       /* CO Z comment NUL */
+    const uint32_t cg_at = tag_at + tc.n + md_len + sa_len + (primary ? 4u + comment : 0u);     /* CO Z comment NUL */
     const uint32_t bytes = cg_at + (lng ? 8u + 4u * n_ops : 0u);                                 /* CG B I count, the words */
     if (S::write) {
         uint8_t *o = sink.out + R.at;
@@ -168,9 +181,13 @@ __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
             if (right) { ByteSink c; c.p = ops + 4ull * (n_ops - 1u); c.n = 0; put_le(c, (right << 4) | clip, 4); }
             ByteSink t; t.p = o + tag_at; t.n = 0;
             bam_tags(t, nm, as);
+            if (md_len) { t.put('M'); t.put('D'); t.put('Z'); t.n += md.text; t.put(0); }          /* the texts are the wave's, below */
+            if (sa_len) { t.put('S'); t.put('A'); t.put('Z'); t.n += sa_len - BRX_BAM_ZTAG; t.put(0); }
             if (primary) { t.put('C'); t.put('O'); t.put('Z'); put_comment(t, d, *sink.M.s, sink.M.pieces); t.put(0); }
             if (lng) { t.put('C'); t.put('G'); t.put('B'); t.put('I'); put_le(t, n_ops, 4); }
         }
+        if (md_len) md_sweep<true>(d, R, q, minus, o + tag_at + tc.n + 3u, md);
+        if (sa_len) sa_write(d, sink.A, line, R.best, o + tag_at + tc.n + md_len + 3u);
         bam_cigar(R, q, ops + (left ? 4u : 0u), sh.runs, minus);
         bam_bases(sink.T, sink.M, o + seq_at, o + qual_at, primary ? 0u : qs, primary ? L : qe, minus);
     } else if (top) {
@@ -183,26 +200,37 @@ __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
 /* bytes of the unmapped record of a read of L bases: the fixed part, SEQ, QUAL, CO:Z: with the comment and its NUL */
 __device__ __forceinline__ uint32_t bam_unmapped_bytes(uint32_t L, uint32_t comment) { return BRX_BAM_CIGAR_AT + bam_bases_bytes(L) + 4u + comment; }
 
-/* bytes and primary record (BRX_SAM_UNMAPPED: none) of every read */
-__global__ void __launch_bounds__(64) k_bam_size(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t max_ops, uint32_t *len, uint32_t *best) {
+/* bytes and primary record (BRX_SAM_UNMAPPED: none) of every read; with SA its records in the table too, as k_sam_size */
+template <uint32_t TAGS>
+__global__ void __launch_bounds__(64) k_bam_size(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t max_ops, uint32_t *len, uint32_t *best,
+                                                  uint32_t *n_rec) {
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
-    PafRead R; R.at = 0; R.best = 0; R.top = 0; R.n_rec = 0;
-    BamCount k_; k_.out = nullptr; k_.surplus = 0; k_.max_ops = max_ops; k_.M = sam_of(s, nullptr, arena); k_.T.fwd = k_.T.rev = 0;
+    PafRead R; R.at = 0; R.best = 0; R.top = 0; R.n_rec = 0; R.frag = nullptr;
+    BamCount<TAGS> k_; k_.A.tab = nullptr; k_.A.n = 0; k_.A.sum = 0; k_.out = nullptr; k_.surplus = 0; k_.max_ops = max_ops; k_.M = sam_of(s, nullptr, arena); k_.T.fwd = k_.T.rev = 0;
     if (paf_has_records(s)) paf_read(k_, d, s, r, segs, arena, R);
     uint32_t bytes = (uint32_t)R.at + k_.surplus, top = R.top;
     if (R.n_rec == 0) { top = BRX_SAM_UNMAPPED; bytes = s.rec_len ? bam_unmapped_bytes(s.seq_len, sam_comment(k_)) : 0u; }
+    if (TAGS & BRX_TAG_SA) {
+        const uint32_t n = R.n_rec >= 2 ? R.n_rec : 0u;
+        bytes += n * BRX_BAM_ZTAG + (n ? n - 1u : 0u) * k_.A.sum;
+        if (lane_id() == 0) n_rec[r] = n;
+    }
     if (lane_id() == 0) { len[r] = bytes; best[r] = top; }
 }
 
+template <uint32_t TAGS>
 __global__ void __launch_bounds__(64) k_bam_write(BrxDev d, const RS *rs, const PSeg *segs, const PPiece *pieces, const uint8_t *arena, uint32_t max_ops,
-                                                   const uint64_t *off, const uint32_t *best, uint8_t *out) {
+                                                   const uint64_t *off, const uint32_t *best, uint8_t *out, const uint8_t *Fbuf,
+                                                   const uint64_t *rec_off, const SaRec *table) {
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
     if (s.rec_len == 0) return;
-    BamWrite w; w.out = out; w.max_ops = max_ops; w.M = sam_of(s, pieces, arena); w.T = bam_nibbles(d);
+    BamWrite<TAGS> w; w.A.tab = nullptr; w.A.n = 0; w.A.sum = 0; w.out = out; w.max_ops = max_ops; w.M = sam_of(s, pieces, arena); w.T = bam_nibbles(d);
     if (best[r] != BRX_SAM_UNMAPPED) {
-        PafRead R; R.at = off[r]; R.best = best[r];
+        PafRead R; R.at = off[r]; R.best = best[r]; R.frag = nullptr;
+        if (TAGS & BRX_TAG_MD) R.frag = Fbuf + s.F_off;
+        if (TAGS & BRX_TAG_SA) w.A = sa_read_of(table, rec_off, r);
         paf_read(w, d, s, r, segs, arena, R);
         return;
     }

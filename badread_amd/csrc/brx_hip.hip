@@ -82,6 +82,8 @@ struct brx_ctx {
     BrxDev paf_dev;
     const RS *paf_rs; const PSeg *paf_segs; uint32_t paf_reads;
     const PPiece *paf_pieces; const uint8_t *paf_seqbuf;      /* brx_emit_sam: what k_emit read the records from */
+    const uint8_t *paf_frags;                                 /* MD:Z: -- the fragments (Fbuf: bottom of the arena, kept until the next batch) */
+    uint8_t *h_sa, *d_sa; size_t sa_bytes;         /* pinned (mapped): SA:Z: -- one SaRec per record of the reads with two or more */
     uint8_t *h_paf, *d_paf; size_t paf_bytes;      /* pinned (mapped): per-read PAF bytes, primary records and offsets */
     char err[512];
 };
@@ -154,6 +156,7 @@ static void release(brx_ctx *c) {
     if (c->h_totals) (void)hipHostFree(c->h_totals);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_paf) (void)hipHostFree(c->h_paf);
+    if (c->h_sa) (void)hipHostFree(c->h_sa);
     free(c);
 }
 
@@ -1057,7 +1060,7 @@ int Batch::run() {
     if ((rc = records())) return rc;
     if (c->ktiming && (rc = kernel_statistics())) return rc;
     if (out_bytes) *out_bytes = (size_t)rec_bytes;
-    if (!raw) { c->paf_dev = dev; c->paf_rs = rs; c->paf_segs = segs; c->paf_reads = n_reads; c->paf_pieces = pieces; c->paf_seqbuf = c->scratch; c->paf_valid = true; }
+    if (!raw) { c->paf_dev = dev; c->paf_rs = rs; c->paf_segs = segs; c->paf_reads = n_reads; c->paf_pieces = pieces; c->paf_seqbuf = c->scratch; c->paf_frags = Fbuf; c->paf_valid = true; }
     /* a read that exhausted its 1000 tries is fatal in the reference (simulate.py:164) */
     if (!raw) {
         { int rc_ = fetch_rs(st); if (rc_) return rc_; }
@@ -1271,15 +1274,20 @@ extern "C" int brx_bgzf_device(brx_ctx *c, const void *d_in, size_t n_bytes, voi
 
 /* ---- truth alignments of the last simulate batch: PAF text (brx_paf.h), SAM records (brx_sam.h) or BAM records (brx_bam.h) ---- */
 enum { TRUTH_PAF = 0, TRUTH_SAM = 1, TRUTH_BAM = 2 };
-static int emit_truth(brx_ctx *c, int kind, uint32_t max_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+/* one instantiation of the SAM / BAM kernels per set of tags: 0 is the untagged code, nothing of the tags in its column loops */
+#define TAGGED(tags, LAUNCH) do { switch (tags) { case 0: { LAUNCH(0u); } break; case 1: { LAUNCH(1u); } break; case 2: { LAUNCH(2u); } break; default: { LAUNCH(3u); } break; } } while (0)
+static int emit_truth(brx_ctx *c, int kind, uint32_t tags, uint32_t max_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
     if (!c || !out_bytes) return BRX_E_ARG;
     *out_bytes = 0;
+    if (tags & ~(uint32_t)(BRX_TAG_MD | BRX_TAG_SA)) return fail(c, BRX_E_ARG, "truth tags %#x: only BRX_TAG_MD | BRX_TAG_SA", tags);
     if (!c->paf_valid) return fail(c, BRX_E_STATE, "no simulate batch on this context to emit truth alignments for");
     hipStream_t st = (hipStream_t)hip_stream;
     HIPCHK(c, hipSetDevice(c->device));
     const uint32_t n = c->paf_reads;
-    const size_t len_at = 0, best_at = ((size_t)n * 4 + 255) & ~(size_t)255, off_at = best_at + (((size_t)n * 4 + 255) & ~(size_t)255);
-    const size_t need = off_at + ((size_t)n + 1) * 8;
+    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t len_at = 0, best_at = pad((size_t)n * 4), off_at = best_at + pad((size_t)n * 4);
+    const size_t nrec_at = off_at + pad(((size_t)n + 1) * 8), recoff_at = nrec_at + pad((size_t)n * 4);       /* SA: records per read and their scan */
+    const size_t need = recoff_at + ((size_t)n + 1) * 8;
     if (c->paf_bytes < need) {
         if (c->h_paf) { (void)hipHostFree(c->h_paf); c->h_paf = c->d_paf = nullptr; c->paf_bytes = 0; }
         HIPCHK(c, hipHostMalloc((void **)&c->h_paf, need, hipHostMallocMapped));
@@ -1287,15 +1295,20 @@ static int emit_truth(brx_ctx *c, int kind, uint32_t max_ops, uint8_t *d_out, si
         HIPCHK(c, hipHostGetDevicePointer(&dp, c->h_paf, 0));
         c->d_paf = (uint8_t *)dp; c->paf_bytes = need;
     }
-    uint32_t *len = (uint32_t *)(c->d_paf + len_at), *best = (uint32_t *)(c->d_paf + best_at);
-    uint64_t *off = (uint64_t *)(c->d_paf + off_at);
+    uint32_t *len = (uint32_t *)(c->d_paf + len_at), *best = (uint32_t *)(c->d_paf + best_at), *n_rec = (uint32_t *)(c->d_paf + nrec_at);
+    uint64_t *off = (uint64_t *)(c->d_paf + off_at), *rec_off = (uint64_t *)(c->d_paf + recoff_at);
     const uint8_t *arena = (const uint8_t *)c->scratch;
-    const bool sam = kind == TRUTH_SAM, bam = kind == TRUTH_BAM;
-    if (n && bam) hipLaunchKernelGGL(k_bam_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, max_ops, len, best);
-    else if (n && sam) hipLaunchKernelGGL(k_sam_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best);
+    const bool sam = kind == TRUTH_SAM, bam = kind == TRUTH_BAM, sa = (tags & BRX_TAG_SA) != 0;
+#define BAM_SIZE(T) hipLaunchKernelGGL((k_bam_size<T>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, max_ops, len, best, n_rec)
+#define SAM_SIZE(T) hipLaunchKernelGGL((k_sam_size<T>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best, n_rec)
+    if (n && bam) TAGGED(tags, BAM_SIZE);
+    else if (n && sam) TAGGED(tags, SAM_SIZE);
     else if (n) hipLaunchKernelGGL(k_paf_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best);
+#undef BAM_SIZE
+#undef SAM_SIZE
     if (sam || bam) hipLaunchKernelGGL(k_sam_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
     else hipLaunchKernelGGL(k_paf_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
+    if (sa) hipLaunchKernelGGL(k_sam_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)n_rec, rec_off);
     { int rcw = wait_stream(c, st, bam ? "k_bam_size" : sam ? "k_sam_size" : "k_paf_size"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
     const uint64_t total = ((const uint64_t *)(c->h_paf + off_at))[n];
@@ -1303,12 +1316,27 @@ static int emit_truth(brx_ctx *c, int kind, uint32_t max_ops, uint8_t *d_out, si
         c->output_needed = total;
         return fail(c, BRX_E_OUTPUT, "truth alignment buffer too small: need %llu bytes", (unsigned long long)total);
     }
-    if (n && total && bam) hipLaunchKernelGGL(k_bam_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf,
-                                              max_ops, (const uint64_t *)off, (const uint32_t *)best, d_out);
-    else if (n && total && sam) hipLaunchKernelGGL(k_sam_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf,
-                                              (const uint64_t *)off, (const uint32_t *)best, d_out);
+    const uint64_t sa_recs = sa ? ((const uint64_t *)(c->h_paf + recoff_at))[n] : 0;
+    if (sa_recs * sizeof(SaRec) > c->sa_bytes) {
+        if (c->h_sa) { (void)hipHostFree(c->h_sa); c->h_sa = c->d_sa = nullptr; c->sa_bytes = 0; }
+        const size_t want = (size_t)(sa_recs + sa_recs / 4 + 1024) * sizeof(SaRec);
+        HIPCHK(c, hipHostMalloc((void **)&c->h_sa, want, hipHostMallocMapped));
+        void *dp = nullptr;
+        HIPCHK(c, hipHostGetDevicePointer(&dp, c->h_sa, 0));
+        c->d_sa = (uint8_t *)dp; c->sa_bytes = want;
+    }
+    SaRec *table = (SaRec *)c->d_sa;
+    if (n && total && sa_recs) hipLaunchKernelGGL(k_sa_fill, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, (const uint64_t *)rec_off, table);
+#define BAM_WRITE(T) hipLaunchKernelGGL((k_bam_write<T>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf, \
+                                        max_ops, (const uint64_t *)off, (const uint32_t *)best, d_out, c->paf_frags, (const uint64_t *)rec_off, (const SaRec *)table)
+#define SAM_WRITE(T) hipLaunchKernelGGL((k_sam_write<T>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf, \
+                                        (const uint64_t *)off, (const uint32_t *)best, d_out, c->paf_frags, (const uint64_t *)rec_off, (const SaRec *)table)
+    if (n && total && bam) TAGGED(tags, BAM_WRITE);
+    else if (n && total && sam) TAGGED(tags, SAM_WRITE);
     else if (n && total) hipLaunchKernelGGL(k_paf_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena,
                                             (const uint64_t *)off, (const uint32_t *)best, d_out);
+#undef BAM_WRITE
+#undef SAM_WRITE
     if (d_read_off) HIPCHK(c, hipMemcpyAsync(d_read_off, c->h_paf + off_at, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
     { int rcw = wait_stream(c, st, bam ? "k_bam_write" : sam ? "k_sam_write" : "k_paf_write"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
@@ -1316,14 +1344,21 @@ static int emit_truth(brx_ctx *c, int kind, uint32_t max_ops, uint8_t *d_out, si
     return BRX_OK;
 }
 extern "C" int brx_emit_paf(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return emit_truth(c, TRUTH_PAF, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+    return emit_truth(c, TRUTH_PAF, 0, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+}
+extern "C" int brx_emit_sam_tags(brx_ctx *c, uint32_t tags, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+    return emit_truth(c, TRUTH_SAM, tags, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
 }
 extern "C" int brx_emit_sam(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return emit_truth(c, TRUTH_SAM, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+    return brx_emit_sam_tags(c, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
 }
-extern "C" int brx_emit_bam(brx_ctx *c, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+extern "C" int brx_emit_bam_tags(brx_ctx *c, uint32_t tags, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes,
+                                 void *hip_stream) {
     if (!c || !out_bytes) return BRX_E_ARG;
     if (max_cigar_ops == 0) max_cigar_ops = 65535;
     if (max_cigar_ops < 2 || max_cigar_ops > 65535) return fail(c, BRX_E_ARG, "brx_emit_bam: max_cigar_ops %u (2..65535, or 0 for 65535)", max_cigar_ops);
-    return emit_truth(c, TRUTH_BAM, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+    return emit_truth(c, TRUTH_BAM, tags, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+}
+extern "C" int brx_emit_bam(brx_ctx *c, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+    return brx_emit_bam_tags(c, 0, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
 }

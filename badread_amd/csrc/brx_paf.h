@@ -30,9 +30,11 @@ __device__ __forceinline__ uint32_t paf_digits(uint32_t v) { uint32_t n = 1; whi
 __device__ __forceinline__ int paf_top(uint64_t bits) { return 63 - __builtin_clzll(bits); }     /* bits != 0 */
 __device__ __forceinline__ uint32_t paf_cls(uint32_t op) { return op <= 1 ? 0u : op; }              /* M (= or X), I, D */
 
-struct PafRec { uint32_t c0, c1, r0; uint64_t key0; };          /* first / last M column, read index and origin of the first */
+struct PafRec { uint32_t c0, c1, r0, f0; uint64_t key0; };      /* first / last M column, read index and origin of the first; f0: its index in the
+                                                                    padded fragment, kept only for a sink that asks (S::need_f0: MD:Z:, brx_sam.h) */
 struct PafRead {                                                 /* what a record needs of its read (uniform over the wave) */
     const uint8_t *ops; uint64_t read; uint32_t seq_len, start_trim;
+    const uint8_t *frag;             /* the padded fragment the read was aligned against (Fbuf + RS.F_off); set by the kernels that write MD:Z: */
     uint32_t best;                   /* the primary record (writing sink: found by the sizing pass) */
     uint32_t n_rec, top, top_set; int64_t top_as; uint64_t at;      /* records so far, the first of the highest AS among them */
 };
@@ -41,11 +43,11 @@ struct PafShape { uint32_t cnt[4], text, runs; };                /* a record's c
 /* The sinks of the walk (paf_read): what is done with every record it closes.  brx_sam.h adds its own two. */
 template <class S> __device__ void paf_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q);
 struct PafCount {
-    static constexpr bool write = false; uint8_t *out;
+    static constexpr bool write = false, need_f0 = false; uint8_t *out;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { paf_record(*this, d, R, q); }
 };
 struct PafWrite {
-    static constexpr bool write = true; uint8_t *out;
+    static constexpr bool write = true, need_f0 = false; uint8_t *out;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { paf_record(*this, d, R, q); }
 };
 
@@ -183,7 +185,7 @@ __device__ void paf_read(S &sink, const BrxDev &d, const RS &s, uint32_t r, cons
     uint32_t r_base = 0, f_base = 0, cur = 0;
     uint64_t carry_key = BRX_PAF_NOKEY, last_m = 0;
     bool carry_good = false, pend = true, open = false;
-    PafRec q; q.c0 = q.c1 = q.r0 = 0; q.key0 = 0;
+    PafRec q; q.c0 = q.c1 = q.r0 = q.f0 = 0; q.key0 = 0;
     for (uint32_t b = 0; b < ncols; b += 64) {
         const uint32_t c = b + lane;
         const bool in = c < ncols;
@@ -227,8 +229,9 @@ __device__ void paf_read(S &sink, const BrxDev &d, const RS &s, uint32_t r, cons
             const uint64_t before = mm & ((1ull << L) - 1ull);
             const uint32_t r0 = wave_bcast_u32(rr, L);
             const uint64_t k0 = wave_bcast_u64(key, L);
+            const uint32_t f0 = S::need_f0 ? wave_bcast_u32(ff, L) : 0u;
             if (open) { q.c1 = before ? b + (uint32_t)paf_top(before) : (uint32_t)last_m; sink.record(d, R, q); }
-            q.c0 = b + (uint32_t)L; q.r0 = r0; q.key0 = k0; open = true;
+            q.c0 = b + (uint32_t)L; q.r0 = r0; q.f0 = f0; q.key0 = k0; open = true;
         }
         if (mm) {
             const int hm = paf_top(mm);

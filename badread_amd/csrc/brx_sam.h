@@ -16,6 +16,16 @@
  * primary (SamCount.surplus); it reads no SEQ or QUAL byte.  k_sam_write knows the primary from the sizing pass.  One wave per
  * read; lane 0 writes the fixed fields, the wave places the CIGAR runs and copies SEQ and QUAL 64 bytes per step (contiguous
  * stores; on '-' lines the loads run backwards).
+ *
+ * brx_emit_sam_tags adds MD:Z: and SA:Z: behind AS:i: (template parameter TAGS of the sinks and kernels; TAGS = 0 is the code above).
+ *   MD  a third sweep over the record's columns (md_sweep): every X column and every D column owns a piece of the text, the wave's
+ *       prefix sum places it; the number in front of an item is the count of '=' columns since the item before it (ballot
+ *       popcounts, carried across steps).  The reference base is the fragment's: Fbuf + RS.F_off is carved from the bottom of the
+ *       arena before anything take_top() hands out and lies under nothing the final stage's slabs reuse, so the bytes the read was
+ *       aligned against are still there when the truth is emitted -- the packed reference is not consulted.
+ *   SA  needs every record of the read before its first line: the sizing pass leaves the records per read, k_sa_fill writes one
+ *       SaRec per record of every read with two or more into the context's table, and a line's value is then written one lane per
+ *       element (sa_write).
  */
 #ifndef BRX_SAM_H
 #define BRX_SAM_H
@@ -25,6 +35,8 @@
 #define BRX_SAM_MATE "\t*\t0\t0\t"                       /* RNEXT PNEXT TLEN, between CIGAR and SEQ */
 #define BRX_SAM_NOMAP "\t4\t*\t0\t0\t*\t*\t0\t0\t"      /* FLAG .. TLEN of an unmapped line */
 #define BRX_SAM_CO "\tCO:Z:"
+#define BRX_SAM_MD "\tMD:Z:"
+#define BRX_SAM_SA "\tSA:Z:"
 #define BRX_SAM_LEN(lit) ((uint32_t)sizeof(lit) - 1u)
 
 /* the fields of a mapped line before its CIGAR, and the clips around it */
@@ -58,19 +70,146 @@ __device__ void sam_bases(const BrxDev &d, const SamRead &M, uint8_t *o, uint32_
     if (lane == 0) o[len] = '\t';
 }
 
+
+/* ---- MD:Z: ---------------------------------------------------------------------------------------------------------------- */
+struct MdShape { uint32_t text, tail; };       /* length of the value; its last number: the '=' columns behind the last item */
+
+/* The sweep over the record [q.c0, q.c1] for MD.  An X column owns "<u><base>", the first column of a D run "<u>^<base>", every
+   other D column "<base>"; u = the '=' columns since the last X or D column (I columns do nothing).  '-' records are mirrored piece
+   by piece: "<base><u>", the '^' goes to the run's LAST column, and the value's last number comes first.  WRITE = false only sizes
+   (no fragment byte is read) and returns the shape that the writing sweep is given.  Every lane calls it. */
+template <bool WRITE>
+__device__ MdShape md_sweep(const BrxDev &d, const PafRead &R, const PafRec &q, bool minus, uint8_t *md, MdShape sh) {
+    const int lane = lane_id();
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint32_t done = 0, carry = 0, f_base = q.f0;
+    for (uint32_t b = q.c0; b <= q.c1; b += 64) {
+        const uint32_t c = b + lane;
+        const bool in = c <= q.c1;
+        const uint32_t op = in ? R.ops[c] : 2u;
+        const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
+        const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
+        const bool isx = in && op == 1u, isd = in && op == 3u;
+        const bool first = isd && prev != 3u, last = isd && next != 3u, owner = isx || first;
+        const uint64_t eq = __ballot(in && op == 0u), brk = __ballot(isx || isd);
+        const uint64_t pb = brk & below;
+        const uint32_t u = pb ? (uint32_t)__popcll(eq & below & ~((2ull << paf_top(pb)) - 1ull)) : carry + (uint32_t)__popcll(eq & below);
+        const uint32_t nd = owner ? paf_digits(u) : 0u;
+        const uint32_t t = ((isx || isd) ? 1u : 0u) + nd + ((minus ? last : first) ? 1u : 0u);
+        if (!WRITE) done += wave_sum(t);
+        else {
+            const uint64_t tm = __ballot(in && op != 2u);
+            const uint32_t incl = wave_incl_scan(t);
+            if (t) {
+                const uint32_t fwd = done + incl - t;
+                const uint32_t code = R.frag[f_base + (uint32_t)__popcll(tm & below)] & 15u;
+                const uint8_t base = d.ref.sym[minus ? d.ref.comp[code] & 15u : code];
+                uint8_t *p = md + (minus ? sh.text - fwd - t : fwd);
+                uint8_t *num = minus ? p + (t - nd) : p;
+                uint32_t v = u;
+                for (uint32_t x = nd; x-- > 0;) { num[x] = (uint8_t)('0' + v % 10); v /= 10; }
+                if (minus) { if (last) p[0] = '^'; p[last ? 1 : 0] = base; }
+                else { if (first) p[nd] = '^'; p[t - 1] = base; }
+            }
+            done += wave_bcast_u32(incl, 63);
+            f_base += (uint32_t)__popcll(tm);
+        }
+        if (brk) carry = (uint32_t)__popcll(eq & ~((2ull << paf_top(brk)) - 1ull)); else carry += (uint32_t)__popcll(eq);
+    }
+    if (!WRITE) { sh.tail = carry; sh.text = done + paf_digits(carry); }
+    else if (lane == 0) {
+        const uint32_t nd = paf_digits(sh.tail);
+        uint8_t *num = minus ? md : md + sh.text - nd;
+        uint32_t v = sh.tail;
+        for (uint32_t x = nd; x-- > 0;) { num[x] = (uint8_t)('0' + v % 10); v /= 10; }
+    }
+    return sh;
+}
+
+/* ---- SA:Z: ---------------------------------------------------------------------------------------------------------------- */
+struct SaRec { uint32_t cs, pos, left, right, q, t, nm, len; };     /* contig << 1 | strand, POS, the clips, M+I, M+D, NM; the length of its element */
+
+/* RNAME,POS,strand,CIGAR,60,NM; -- the CIGAR in the compact form: the clips as S, one M, and the surplus of either side as one I or D */
+template <class B>
+__device__ void sa_element(B &b, const BrxDev &d, const SaRec &e) {
+    const brx_contig ct = d.ref.d_contigs[e.cs >> 1];
+    for (uint32_t x = 0; x < ct.name_len; ++x) b.put(d.ref.d_names[ct.name_off + x]);
+    b.put(','); put_dec(b, e.pos); b.put(','); b.put((e.cs & 1u) ? '-' : '+'); b.put(',');
+    if (e.left) { put_dec(b, e.left); b.put('S'); }
+    put_dec(b, e.q < e.t ? e.q : e.t); b.put('M');
+    if (e.q > e.t) { put_dec(b, e.q - e.t); b.put('I'); } else if (e.t > e.q) { put_dec(b, e.t - e.q); b.put('D'); }
+    if (e.right) { put_dec(b, e.right); b.put('S'); }
+    put_str(b, ",60,"); put_dec(b, e.nm); b.put(';');
+}
+
+/* what the other lines of the read say about the record q of shape sh */
+__device__ SaRec sa_rec_of(const BrxDev &d, const PafRead &R, const PafRec &q, const PafShape &sh) {
+    const uint32_t cs = (uint32_t)(q.key0 >> 32), p0 = (uint32_t)q.key0;
+    const uint32_t qcols = sh.cnt[0] + sh.cnt[1] + sh.cnt[2], tspan = sh.cnt[0] + sh.cnt[1] + sh.cnt[3];
+    const uint32_t qs = q.r0 - R.start_trim, qe = qs + qcols;
+    SaRec e; e.cs = cs;
+    e.pos = ((cs & 1u) ? d.ref.d_contigs[cs >> 1].length - p0 - tspan : p0) + 1u;
+    e.left = (cs & 1u) ? R.seq_len - qe : qs; e.right = (cs & 1u) ? qs : R.seq_len - qe;
+    e.q = qcols; e.t = tspan; e.nm = sh.cnt[1] + sh.cnt[2] + sh.cnt[3];
+    CountSink k_; k_.n = 0; sa_element(k_, d, e);
+    e.len = k_.n;
+    return e;
+}
+
+/* the sink of k_sa_fill: record i of the read goes to tab[i] */
+struct SaFill {
+    static constexpr bool write = false, need_f0 = false; SaRec *tab;
+    __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) {
+        const PafShape sh = paf_shape(R, q);
+        const SaRec e = sa_rec_of(d, R, q, sh);
+        if (lane_id() == 0) tab[R.n_rec] = e;
+        R.n_rec += 1;
+    }
+};
+
+/* The table of a read's n records (n >= 2, or 0: no SA), and the sum of their elements' lengths. */
+struct SaRead { const SaRec *tab; uint32_t n, sum; };
+__device__ SaRead sa_read_of(const SaRec *table, const uint64_t *rec_off, uint32_t r) {
+    SaRead A; A.tab = table + rec_off[r]; A.n = (uint32_t)(rec_off[r + 1] - rec_off[r]); A.sum = 0;
+    for (uint32_t base = 0; base < A.n; base += 64) {
+        const uint32_t j = base + (uint32_t)lane_id();
+        A.sum += wave_sum(j < A.n ? A.tab[j].len : 0u);
+    }
+    return A;
+}
+
+/* The SA value of line i at o: the primary's element first unless i is the primary, then the others in line order; one lane per
+   element, placed by the prefix sum of the lengths.  Every lane calls it. */
+__device__ void sa_write(const BrxDev &d, const SaRead &A, uint32_t i, uint32_t best, uint8_t *o) {
+    const uint32_t lane = (uint32_t)lane_id();
+    uint32_t done = i != best ? A.tab[best].len : 0u;
+    for (uint32_t base = 0; base < A.n; base += 64) {
+        const uint32_t j = base + lane;
+        const bool have = j < A.n && j != i, lead = have && j == best;
+        SaRec e{};
+        if (have) e = A.tab[j];
+        const uint32_t len = lead ? 0u : e.len;
+        const uint32_t incl = wave_incl_scan(len);
+        if (have) { ByteSink s_; s_.p = o + (lead ? 0u : done + incl - len); s_.n = 0; sa_element(s_, d, e); }
+        done += wave_bcast_u32(incl, 63);
+    }
+}
+
 template <class S> __device__ void sam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q);
-struct SamCount {
-    static constexpr bool write = false; uint8_t *out; SamRead M; uint32_t surplus;
+template <uint32_t TAGS> struct SamCount {
+    static constexpr bool write = false, need_f0 = (TAGS & BRX_TAG_MD) != 0; static constexpr uint32_t tags = TAGS;
+    uint8_t *out; SamRead M; uint32_t surplus; SaRead A;             /* A.sum: the elements' lengths of the records so far */
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { sam_record(*this, d, R, q); }
 };
-struct SamWrite {
-    static constexpr bool write = true; uint8_t *out; SamRead M;
+template <uint32_t TAGS> struct SamWrite {
+    static constexpr bool write = true, need_f0 = (TAGS & BRX_TAG_MD) != 0; static constexpr uint32_t tags = TAGS;
+    uint8_t *out; SamRead M; SaRead A;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { sam_record(*this, d, R, q); }
 };
 /* the comment's length: the FASTQ header is '@', the name, a blank, the comment and a newline (RS.hdr_len, k_recsize) */
 template <class S> __device__ __forceinline__ uint32_t sam_comment(const S &sink) { return sink.M.s->hdr_len - (BRX_SAM_NAME + 3u); }
-__device__ __forceinline__ void sink_surplus(SamCount &k, uint32_t v) { k.surplus = v; }
-__device__ __forceinline__ void sink_surplus(SamWrite &, uint32_t) {}
+template <uint32_t TAGS> __device__ __forceinline__ void sink_surplus(SamCount<TAGS> &k, uint32_t v) { k.surplus = v; }
+template <uint32_t TAGS> __device__ __forceinline__ void sink_surplus(SamWrite<TAGS> &, uint32_t) {}
 
 
 /* One record of the read as a SAM line: sized (as a supplementary line; the primary's surplus goes with the best AS), or
@@ -84,8 +223,17 @@ __device__ void sam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
     const bool minus = ((q.key0 >> 32) & 1u) != 0;
     const uint32_t L = R.seq_len, qs = q.r0 - R.start_trim, qe = qs + qcols;
     const uint32_t left = minus ? L - qe : qs, right = minus ? qs : L - qe;
-    const bool primary = S::write && R.n_rec == R.best;
+    const uint32_t line = R.n_rec;
+    const bool primary = S::write && line == R.best;
     const bool top = paf_rank(R, as);
+    /* MD:Z: and SA:Z: (a sized line counts no SA: k_sam_size adds the read's at the end) */
+    MdShape md; md.text = md.tail = 0;
+    uint32_t md_len = 0, sa_len = 0;
+    if (S::tags & BRX_TAG_MD) { md = md_sweep<false>(d, R, q, minus, nullptr, md); md_len = BRX_SAM_LEN(BRX_SAM_MD) + md.text; }
+    if (S::tags & BRX_TAG_SA) {
+        if (!S::write) sink.A.sum += sa_rec_of(d, R, q, sh).len;
+        else if (sink.A.n) sa_len = BRX_SAM_LEN(BRX_SAM_SA) + sink.A.sum - sink.A.tab[line].len;
+    }
     CountSink hc; hc.n = 0;
     sam_head(hc, d, R, q, tspan, primary);
     CountSink lc; lc.n = 0; sam_clip(lc, left, primary);
@@ -94,7 +242,7 @@ __device__ void sam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
     const uint32_t comment = sam_comment(sink);
     const uint32_t bases = primary ? L : qcols;
     const uint32_t cig_at = hc.n + lc.n, seq_at = cig_at + sh.text + rc.n + BRX_SAM_LEN(BRX_SAM_MATE), tag_at = seq_at + 2u * bases + 1u;
-    const uint32_t bytes = tag_at + tc.n + (primary ? BRX_SAM_LEN(BRX_SAM_CO) + comment : 0u) + 1u;
+    const uint32_t bytes = tag_at + tc.n + md_len + sa_len + (primary ? BRX_SAM_LEN(BRX_SAM_CO) + comment : 0u) + 1u;
     if (S::write) {
         uint8_t *o = sink.out + R.at;
         if (lane_id() == 0) {
@@ -104,9 +252,13 @@ __device__ void sam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
             sam_clip(m, right, primary); put_str(m, BRX_SAM_MATE);
             ByteSink t; t.p = o + tag_at; t.n = 0;
             paf_tags(t, nm, as);
+            if (md_len) { put_str(t, BRX_SAM_MD); t.n += md.text; }            /* the values are the wave's, below */
+            if (sa_len) { put_str(t, BRX_SAM_SA); t.n += sa_len - BRX_SAM_LEN(BRX_SAM_SA); }
             if (primary) { put_str(t, BRX_SAM_CO); put_comment(t, d, *sink.M.s, sink.M.pieces); }
             t.put('\n');
         }
+        if (md_len) md_sweep<true>(d, R, q, minus, o + tag_at + tc.n + BRX_SAM_LEN(BRX_SAM_MD), md);
+        if (sa_len) sa_write(d, sink.A, line, R.best, o + tag_at + tc.n + md_len + BRX_SAM_LEN(BRX_SAM_SA));
         paf_cigar(R, q, o + cig_at, sh.text, minus);
         sam_bases(d, sink.M, o + seq_at, primary ? 0u : qs, primary ? L : qe, minus);
     } else if (top) {
@@ -128,16 +280,33 @@ __device__ __forceinline__ SamRead sam_of(const RS &s, const PPiece *pieces, con
     return M;
 }
 
-/* bytes and primary record (BRX_SAM_UNMAPPED: none) of every read */
-__global__ void __launch_bounds__(64) k_sam_size(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t *len, uint32_t *best) {
+/* bytes and primary record (BRX_SAM_UNMAPPED: none) of every read; with SA its records in the table too (n_rec: 0 below two) */
+template <uint32_t TAGS>
+__global__ void __launch_bounds__(64) k_sam_size(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t *len, uint32_t *best,
+                                                  uint32_t *n_rec) {
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
-    PafRead R; R.at = 0; R.best = 0; R.top = 0; R.n_rec = 0;
-    SamCount k_; k_.out = nullptr; k_.surplus = 0; k_.M = sam_of(s, nullptr, arena);
+    PafRead R; R.at = 0; R.best = 0; R.top = 0; R.n_rec = 0; R.frag = nullptr;
+    SamCount<TAGS> k_; k_.out = nullptr; k_.surplus = 0; k_.M = sam_of(s, nullptr, arena); k_.A.tab = nullptr; k_.A.n = 0; k_.A.sum = 0;
     if (paf_has_records(s)) paf_read(k_, d, s, r, segs, arena, R);
     uint32_t bytes = (uint32_t)R.at + k_.surplus, top = R.top;
     if (R.n_rec == 0) { top = BRX_SAM_UNMAPPED; bytes = s.rec_len ? sam_unmapped_bytes(s.seq_len, sam_comment(k_)) : 0u; }
+    if (TAGS & BRX_TAG_SA) {
+        const uint32_t n = R.n_rec >= 2 ? R.n_rec : 0u;               /* every line: the tag and the elements of the n - 1 others */
+        bytes += n * BRX_SAM_LEN(BRX_SAM_SA) + (n ? n - 1u : 0u) * k_.A.sum;
+        if (lane_id() == 0) n_rec[r] = n;
+    }
     if (lane_id() == 0) { len[r] = bytes; best[r] = top; }
+}
+
+/* the SA table: one SaRec per record of every read that the sizing pass counted in (rec_off: the scan of its n_rec) */
+__global__ void __launch_bounds__(64) k_sa_fill(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, const uint64_t *rec_off, SaRec *table) {
+    const uint32_t r = blockIdx.x;
+    if (rec_off[r + 1] == rec_off[r]) return;
+    const RS s = rs[r];
+    PafRead R; R.at = 0; R.best = 0; R.top = 0; R.n_rec = 0; R.frag = nullptr;
+    SaFill f_; f_.tab = table + rec_off[r];
+    paf_read(f_, d, s, r, segs, arena, R);
 }
 
 /* read offsets: off[r] (n_reads + 1 entries, the last = total bytes); the running sums are 64 bits throughout */
@@ -159,14 +328,18 @@ __global__ void __launch_bounds__(64) k_sam_scan(uint32_t n_reads, const uint32_
     if (lane == 0) off[n_reads] = run;
 }
 
+template <uint32_t TAGS>
 __global__ void __launch_bounds__(64) k_sam_write(BrxDev d, const RS *rs, const PSeg *segs, const PPiece *pieces, const uint8_t *arena,
-                                                   const uint64_t *off, const uint32_t *best, uint8_t *out) {
+                                                   const uint64_t *off, const uint32_t *best, uint8_t *out, const uint8_t *Fbuf,
+                                                   const uint64_t *rec_off, const SaRec *table) {
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
     if (s.rec_len == 0) return;
-    SamWrite w; w.out = out; w.M = sam_of(s, pieces, arena);
+    SamWrite<TAGS> w; w.out = out; w.M = sam_of(s, pieces, arena); w.A.tab = nullptr; w.A.n = 0; w.A.sum = 0;
     if (best[r] != BRX_SAM_UNMAPPED) {
-        PafRead R; R.at = off[r]; R.best = best[r];
+        PafRead R; R.at = off[r]; R.best = best[r]; R.frag = nullptr;
+        if (TAGS & BRX_TAG_MD) R.frag = Fbuf + s.F_off;
+        if (TAGS & BRX_TAG_SA) w.A = sa_read_of(table, rec_off, r);
         paf_read(w, d, s, r, segs, arena, R);
         return;
     }

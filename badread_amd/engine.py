@@ -84,6 +84,15 @@ PAF_SHARE = 0.1
 SAM_SHARE = 1.5
 # --truth-bam: the same for a batch's BAM records before they are compressed (measured 1.14 on configs[3]: profiles/truth_bam.md)
 BAM_SHARE = 1.2
+# --truth-tags: what MD:Z: / SA:Z: add to a batch's SAM or BAM records, per FASTQ byte (measured 0.0574-0.0578 and 0.0097-0.0099 on
+# configs[3], the same within 0.0003 in BAM: profiles/truth_tags.md; MD grows with the error rate, and E_OUTPUT's retry is behind it)
+TAG_MD, TAG_SA = 1, 2                  # include/brx.h: BRX_TAG_MD, BRX_TAG_SA
+MD_SHARE = 0.065
+SA_SHARE = 0.012
+
+
+def tag_share(tags):
+    return (MD_SHARE if tags & TAG_MD else 0.0) + (SA_SHARE if tags & TAG_SA else 0.0)
 E_SCRATCH, E_OUTPUT, E_NOFRAG = -3, -4, -5
 STAGE_NAMES = ('plan', 'build', 'mutate', 'scan', 'final', 'emit', 'align1', 'qscore')
 # kernel classes of brx_last_kernel_stats (include/brx.h: BRX_KERN_*), with the names a rocprofv3 kernel trace shows
@@ -300,6 +309,10 @@ def bind_library(lib):
     lib.brx_emit_sam.argtypes = lib.brx_emit_paf.argtypes
     lib.brx_emit_bam.restype = ctypes.c_int
     lib.brx_emit_bam.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + list(lib.brx_emit_paf.argtypes[1:])
+    lib.brx_emit_sam_tags.restype = ctypes.c_int
+    lib.brx_emit_sam_tags.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + list(lib.brx_emit_paf.argtypes[1:])
+    lib.brx_emit_bam_tags.restype = ctypes.c_int
+    lib.brx_emit_bam_tags.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32] + list(lib.brx_emit_paf.argtypes[1:])
     lib.brx_bgzf_device_bound.restype = ctypes.c_size_t
     lib.brx_bgzf_device_bound.argtypes = [ctypes.c_size_t]
     lib.brx_bgzf_device_scratch.restype = ctypes.c_size_t
@@ -553,16 +566,18 @@ class HipEngine(EngineBase):
         entries).  The tensor is a fresh one: the engine may take its next batch at once."""
         return self._emit_truth(self.lib.brx_emit_paf, PAF_SHARE, n_reads)
 
-    def emit_sam_device(self, n_reads):
+    def emit_sam_device(self, n_reads, tags=0):
         """The same truth as SAM records (include/brx.h brx_emit_sam; no header), with emit_paf_device's arguments and results.
-        Both may be called for one batch, in either order."""
-        return self._emit_truth(self.lib.brx_emit_sam, SAM_SHARE, n_reads)
+        Both may be called for one batch, in either order.  `tags`: TAG_MD | TAG_SA adds MD:Z: / SA:Z: (brx_emit_sam_tags)."""
+        emit = lambda ctx, *rest: self.lib.brx_emit_sam_tags(ctx, int(tags), *rest)
+        return self._emit_truth(emit, SAM_SHARE + tag_share(tags), n_reads)
 
-    def emit_bam_device(self, n_reads, max_cigar_ops=65535):
+    def emit_bam_device(self, n_reads, max_cigar_ops=65535, tags=0):
         """The same truth as uncompressed BAM records (include/brx.h brx_emit_bam; no header), one per SAM line, with
-        emit_paf_device's arguments and results.  A record with more than `max_cigar_ops` CIGAR operations takes the CG:B:I form."""
-        emit = lambda ctx, *rest: self.lib.brx_emit_bam(ctx, int(max_cigar_ops), *rest)
-        return self._emit_truth(emit, BAM_SHARE, n_reads)
+        emit_paf_device's arguments and results.  A record with more than `max_cigar_ops` CIGAR operations takes the CG:B:I form;
+        `tags` as for emit_sam_device (brx_emit_bam_tags)."""
+        emit = lambda ctx, *rest: self.lib.brx_emit_bam_tags(ctx, int(tags), int(max_cigar_ops), *rest)
+        return self._emit_truth(emit, BAM_SHARE + tag_share(tags), n_reads)
 
     def bgzf_device(self, data):
         """brx_bgzf_device: a uint8 tensor on this engine's device -> a uint8 tensor (same device) holding BGZF blocks of it, one per

@@ -380,6 +380,21 @@ int brx_emit_sam(brx_ctx *ctx, uint8_t *d_out, size_t out_cap, uint64_t *d_read_
 int brx_emit_bam(brx_ctx *ctx, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes,
                  void *hip_stream);
 
+/* brx_emit_sam / brx_emit_bam with MD:Z: and / or SA:Z: behind AS (tags: BRX_TAG_MD | BRX_TAG_SA; 0 = exactly the functions above,
+ * any other bit BRX_E_ARG), under the same contract; stateless, callable in any order with the other emitters, which stay byte-
+ * identical.  Tag order NM AS [MD] [SA] [CO], then CG in a long-CIGAR BAM record; in BAM both are Z tags.  Unmapped lines get neither.
+ *   MD  on every mapped line, samtools' rule: the '=' columns as numbers, a mismatch as the reference base, a run of deleted
+ *       reference bases behind '^', a 0 between adjacent items and at an end that is a mismatch.  The reference base is the base of
+ *       the fragment the read was aligned against (what NM counts by), through brx_reference.sym; on '-' lines complemented through
+ *       brx_reference.comp, columns from the record's last to its first.  Clips take no part.
+ *   SA  on every mapped line of a read with two or more: `RNAME,POS,strand,CIGAR,60,NM;` for each OTHER mapped line, the primary's
+ *       first, the rest in line order.  CIGAR is the compact form `[left]S min(Q,T)M |Q-T|I-or-D [right]S` (Q = M + I, T = M + D
+ *       lengths; clips always S).  Contig names are copied as they are (README: --truth-tags). */
+enum { BRX_TAG_MD = 1u, BRX_TAG_SA = 2u };
+int brx_emit_sam_tags(brx_ctx *ctx, uint32_t tags, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream);
+int brx_emit_bam_tags(brx_ctx *ctx, uint32_t tags, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off,
+                      size_t *out_bytes, void *hip_stream);
+
 /* n_bytes of device memory as BGZF blocks (SAM spec v1 section 4.1) back to back, one per BRX_BGZF_BLOCK input bytes, the last
  * one possibly shorter, none for no input: the members of brx_gzip_device (one dynamic Huffman code per block, no match search)
  * behind the 18-byte BGZF header (FEXTRA, 'B' 'C', BSIZE = the block's size - 1).  A block needs at most 61 607 bytes, so every
