@@ -101,6 +101,12 @@ SIMULATE_OPTIONS = [
                               help='Tags to add to the records of --truth-sam and --truth-bam, a comma-separated list of MD and SA: '
                                    'MD:Z: (mismatched and deleted reference bases) on every mapped line, SA:Z: (the read\'s other '
                                    'alignments) on every mapped line of a read with two or more')),
+        ('--truth-cs', dict(type=str, default=None, dest='truth_cs', metavar='MODE',
+                            help='Add minimap2\'s cs:Z: tag to every record of --truth-paf and every mapped line of --truth-sam and '
+                                 '--truth-bam: short (:n for matching stretches) or long (=ACGT, the matching bases spelt out)')),
+        ('--truth-eqx', dict(action='store_true', default=False, dest='truth_eqx',
+                             help='Write the CIGARs of --truth-paf, --truth-sam and --truth-bam with = and X in place of M '
+                                  '(such a PAF is not input for error_model / qscore_model)')),
         ('--gpu-streams', dict(type=int, default=None, dest='gpu_streams',
                                help='Device batches in flight per GPU, each on its own HIP stream (default: 6)')),
     ]),
@@ -189,6 +195,19 @@ def truth_tags_mask(text, has_file):
     return sum({TRUTH_TAGS[x] for x in parts})
 
 
+FMT_EQX, FMT_CS, FMT_CS_LONG = 1, 2, 4   # include/brx.h: BRX_FMT_EQX, BRX_FMT_CS, BRX_FMT_CS_LONG
+
+
+def truth_fmt_mask(cs, eqx, has_file):
+    """--truth-cs MODE and --truth-eqx as the bit mask simulate() reads (0 without the options)."""
+    if cs is not None and cs not in ('short', 'long'):
+        sys.exit('Error: --truth-cs must be short or long')
+    for on, flag in ((cs is not None, '--truth-cs'), (eqx, '--truth-eqx')):
+        if on and not has_file:
+            sys.exit(f'Error: {flag} needs --truth-paf, --truth-sam or --truth-bam')
+    return (FMT_EQX if eqx else 0) | (0 if cs is None else FMT_CS if cs == 'short' else FMT_CS | FMT_CS_LONG)
+
+
 def check_simulate_args(args):
     """Validate and derive the fields simulate() reads (mean_frag_length, identity triple, glitch_*)."""
     if not pathlib.Path(args.reference).is_file():
@@ -198,6 +217,8 @@ def check_simulate_args(args):
         if path is not None and not pathlib.Path(path).resolve().parent.is_dir():
             sys.exit(f'Error: the directory of --{flag.replace("_", "-")} {path} does not exist')
     args.truth_tags = truth_tags_mask(getattr(args, 'truth_tags', None), getattr(args, 'truth_sam', None) or getattr(args, 'truth_bam', None))
+    args.truth_fmt = truth_fmt_mask(getattr(args, 'truth_cs', None), bool(getattr(args, 'truth_eqx', False)),
+                                    any(getattr(args, flag, None) for flag in ('truth_paf', 'truth_sam', 'truth_bam')))
     for value, names, flag in ((args.error_model, ERROR_MODEL_NAMES, '--error_model'),
                                (args.qscore_model, QSCORE_MODEL_NAMES, '--qscore_model')):
         if value.lower() not in names and not pathlib.Path(value).is_file():

@@ -7,8 +7,9 @@
  * nothing aligned (the name is 37 bytes: the CIGAR words start at an odd offset), so every store is a byte store.
  *
  *   block_size refID pos l_read_name=37 mapq bin n_cigar_op flag l_seq next_refID=-1 next_pos=-1 tlen=0 name\0
- *   cigar (len << 4 | op, MIDNSH = 0..5)   seq (two bases per byte, '=ACMGRSVTWYHKDBN')   qual (FASTQ character - 33)
- *   NM AS [MD:Z:text\0] [SA:Z:text\0] [CO:Z:comment\0] [CG:B:I]     (integers in the smallest type, htslib's rule; MD and SA:
+ *   cigar (len << 4 | op, MIDNSH = 0..5; with BRX_FMT_EQX = 7 and X 8 for M)
+ *    seq (two bases per byte, '=ACMGRSVTWYHKDBN')   qual (FASTQ character - 33)
+ *   NM AS [MD:Z:text\0] [cs:Z:text\0] [SA:Z:text\0] [CO:Z:comment\0] [CG:B:I]     (integers in the smallest type, htslib's rule; MD and SA:
  *                                            brx_emit_bam_tags, the texts of brx_sam.h's md_sweep and sa_write)
  *
  * A record with more than max_ops CIGAR operations, clips included, takes the long form of section 4.2.2: the CIGAR field holds
@@ -25,7 +26,7 @@
 
 #define BRX_BAM_CIGAR_AT 73u           /* block_size + 32 bytes of fixed fields + the name and its NUL */
 #define BRX_BAM_UNMAPPED_BIN 4680u     /* reg2bin(-1, 0) */
-enum { BAM_OP_M = 0, BAM_OP_I = 1, BAM_OP_D = 2, BAM_OP_N = 3, BAM_OP_S = 4, BAM_OP_H = 5 };
+enum { BAM_OP_M = 0, BAM_OP_I = 1, BAM_OP_D = 2, BAM_OP_N = 3, BAM_OP_S = 4, BAM_OP_H = 5, BAM_OP_EQ = 7, BAM_OP_X = 8 };
 
 template <class B> __device__ void put_le(B &b, uint64_t v, int bytes) { for (int i = 0; i < bytes; ++i) b.put((uint8_t)(v >> (8 * i))); }
 
@@ -93,6 +94,7 @@ __device__ void bam_bases(const BamNib &T, const SamRead &M, uint8_t *seq, uint8
 
 /* Sweep 2 of a record, binary: the lane whose column ends run i stores that run's word at ops[i] ('-' records: at ops[runs - 1 - i]),
    byte by byte.  The runs are paf_cigar's. */
+template <bool EQX>
 __device__ void bam_cigar(const PafRead &R, const PafRec &q, uint8_t *ops, uint32_t runs, bool minus) {
     const int lane = lane_id();
     const uint64_t below = (1ull << lane) - 1ull;
@@ -103,14 +105,15 @@ __device__ void bam_cigar(const PafRead &R, const PafRec &q, uint8_t *ops, uint3
         const uint32_t op = in ? R.ops[c] : 0u;
         const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
         const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
-        const bool rs = in && (c == q.c0 || paf_cls(prev) != paf_cls(op));
-        const bool re = in && (c == q.c1 || paf_cls(next) != paf_cls(op));
+        const bool rs = in && (c == q.c0 || paf_run<EQX>(prev) != paf_run<EQX>(op));
+        const bool re = in && (c == q.c1 || paf_run<EQX>(next) != paf_run<EQX>(op));
         const uint64_t rmask = __ballot(rs), emask = __ballot(re);
         const uint64_t mine = rmask & (below | (1ull << lane));
         const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
         if (re) {
-            const uint32_t i = done + (uint32_t)__popcll(emask & below), cl = paf_cls(op);
-            const uint32_t word = ((c - s0 + 1u) << 4) | (cl == 0 ? (uint32_t)BAM_OP_M : cl == 2 ? (uint32_t)BAM_OP_I : (uint32_t)BAM_OP_D);
+            const uint32_t i = done + (uint32_t)__popcll(emask & below);
+            const uint32_t code = op == 2 ? (uint32_t)BAM_OP_I : op == 3 ? (uint32_t)BAM_OP_D : !EQX ? (uint32_t)BAM_OP_M : op == 0 ? (uint32_t)BAM_OP_EQ : (uint32_t)BAM_OP_X;
+            const uint32_t word = ((c - s0 + 1u) << 4) | code;
             uint8_t *p = ops + 4ull * (minus ? runs - 1u - i : i);
             p[0] = (uint8_t)word; p[1] = (uint8_t)(word >> 8); p[2] = (uint8_t)(word >> 16); p[3] = (uint8_t)(word >> 24);
         }
@@ -120,18 +123,18 @@ __device__ void bam_cigar(const PafRead &R, const PafRec &q, uint8_t *ops, uint3
 }
 
 template <class S> __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q);
-template <uint32_t TAGS> struct BamCount {
-    static constexpr bool write = false, need_f0 = (TAGS & BRX_TAG_MD) != 0; static constexpr uint32_t tags = TAGS;
-    uint8_t *out; SamRead M; uint32_t max_ops, surplus; BamNib T; SaRead A;
+template <uint32_t TAGS, bool F> struct BamCount {                       /* F: with BRX_FMT_* bits, as brx_sam.h's sinks */
+    static constexpr bool write = false, fmtd = F, need_f0 = (TAGS & BRX_TAG_MD) != 0 || F; static constexpr uint32_t tags = TAGS;
+    uint8_t *out; SamRead M; uint32_t max_ops, surplus, fmt; BamNib T; SaRead A;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { bam_record(*this, d, R, q); }
 };
-template <uint32_t TAGS> struct BamWrite {
-    static constexpr bool write = true, need_f0 = (TAGS & BRX_TAG_MD) != 0; static constexpr uint32_t tags = TAGS;
-    uint8_t *out; SamRead M; uint32_t max_ops; BamNib T; SaRead A;
+template <uint32_t TAGS, bool F> struct BamWrite {
+    static constexpr bool write = true, fmtd = F, need_f0 = (TAGS & BRX_TAG_MD) != 0 || F; static constexpr uint32_t tags = TAGS;
+    uint8_t *out; SamRead M; uint32_t max_ops, fmt; BamNib T; SaRead A;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { bam_record(*this, d, R, q); }
 };
-template <uint32_t TAGS> __device__ __forceinline__ void sink_surplus(BamCount<TAGS> &k, uint32_t v) { k.surplus = v; }
-template <uint32_t TAGS> __device__ __forceinline__ void sink_surplus(BamWrite<TAGS> &, uint32_t) {}
+template <uint32_t TAGS, bool F> __device__ __forceinline__ void sink_surplus(BamCount<TAGS, F> &k, uint32_t v) { k.surplus = v; }
+template <uint32_t TAGS, bool F> __device__ __forceinline__ void sink_surplus(BamWrite<TAGS, F> &, uint32_t) {}
 #define BRX_BAM_ZTAG 4u                /* a Z tag around its text: two letters, 'Z' and the NUL */
 
 __device__ __forceinline__ uint32_t bam_bases_bytes(uint32_t l_seq) { return (l_seq + 1u) / 2u + l_seq; }       /* SEQ and QUAL */
@@ -140,7 +143,9 @@ __device__ __forceinline__ uint32_t bam_bases_bytes(uint32_t l_seq) { return (l_
    written.  Every lane calls it (wave-uniform arguments). */
 template <class S>
 __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q) {
-    const PafShape sh = paf_shape(R, q);
+    const uint32_t fmt = sink_fmt(sink);
+    const bool eqx = (fmt & BRX_FMT_EQX) != 0;
+    const PafShape sh = eqx ? paf_shape<true>(R, q) : paf_shape<false>(R, q);     /* with EQX the runs, and so the long form, are the =/X CIGAR's */
     const uint32_t nm = sh.cnt[1] + sh.cnt[2] + sh.cnt[3];
     const int64_t as = (int64_t)sh.cnt[0] - (int64_t)nm;
     const uint32_t qcols = sh.cnt[0] + sh.cnt[1] + sh.cnt[2], tspan = sh.cnt[0] + sh.cnt[1] + sh.cnt[3];
@@ -158,6 +163,11 @@ __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
         if (!S::write) sink.A.sum += sa_rec_of(d, R, q, sh).len;
         else if (sink.A.n) sa_len = BRX_BAM_ZTAG + sink.A.sum - sink.A.tab[line].len;
     }
+    uint32_t cs_text = 0, cs_len = 0;                                                 /* cs as a Z tag between MD and SA */
+    if constexpr (S::fmtd) if (fmt & BRX_FMT_CS) {
+        cs_text = cs_sweep<false>(d, R, q, minus, (fmt & BRX_FMT_CS_LONG) != 0, nullptr, nullptr, 0u);
+        cs_len = BRX_BAM_ZTAG + cs_text;
+    }
     const uint32_t n_ops = sh.runs + (left ? 1u : 0u) + (right ? 1u : 0u);
     const bool lng = n_ops > sink.max_ops;
     const uint32_t n_cigar = lng ? 2u : n_ops;
@@ -165,7 +175,7 @@ __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
     const uint32_t bases = primary ? L : qcols;
     CountSink tc; tc.n = 0; bam_tags(tc, nm, as);
     const uint32_t seq_at = BRX_BAM_CIGAR_AT + 4u * n_cigar, qual_at = seq_at + (bases + 1u) / 2u, tag_at = qual_at + bases;
-    const uint32_t cg_at = tag_at + tc.n + md_len + sa_len + (primary ? 4u + comment : 0u);     /* CO Z comment NUL */
+    const uint32_t cg_at = tag_at + tc.n + md_len + cs_len + sa_len + (primary ? 4u + comment : 0u);     /* CO Z comment NUL */
     const uint32_t bytes = cg_at + (lng ? 8u + 4u * n_ops : 0u);                                 /* CG B I count, the words */
     if (S::write) {
         uint8_t *o = sink.out + R.at;
@@ -182,13 +192,16 @@ __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
             ByteSink t; t.p = o + tag_at; t.n = 0;
             bam_tags(t, nm, as);
             if (md_len) { t.put('M'); t.put('D'); t.put('Z'); t.n += md.text; t.put(0); }          /* the texts are the wave's, below */
+            if (cs_len) { t.put('c'); t.put('s'); t.put('Z'); t.n += cs_text; t.put(0); }
             if (sa_len) { t.put('S'); t.put('A'); t.put('Z'); t.n += sa_len - BRX_BAM_ZTAG; t.put(0); }
             if (primary) { t.put('C'); t.put('O'); t.put('Z'); put_comment(t, d, *sink.M.s, sink.M.pieces); t.put(0); }
             if (lng) { t.put('C'); t.put('G'); t.put('B'); t.put('I'); put_le(t, n_ops, 4); }
         }
         if (md_len) md_sweep<true>(d, R, q, minus, o + tag_at + tc.n + 3u, md);
-        if (sa_len) sa_write(d, sink.A, line, R.best, o + tag_at + tc.n + md_len + 3u);
-        bam_cigar(R, q, ops + (left ? 4u : 0u), sh.runs, minus);
+        if constexpr (S::fmtd) if (cs_len)
+            cs_sweep<true>(d, R, q, minus, (fmt & BRX_FMT_CS_LONG) != 0, sink.M.seq, o + tag_at + tc.n + md_len + 3u, cs_text);
+        if (sa_len) sa_write(d, sink.A, line, R.best, o + tag_at + tc.n + md_len + cs_len + 3u);
+        if (eqx) bam_cigar<true>(R, q, ops + (left ? 4u : 0u), sh.runs, minus); else bam_cigar<false>(R, q, ops + (left ? 4u : 0u), sh.runs, minus);
         bam_bases(sink.T, sink.M, o + seq_at, o + qual_at, primary ? 0u : qs, primary ? L : qe, minus);
     } else if (top) {
         /* the same record as the primary: SEQ and QUAL are the whole read, CO:Z:; the operations stay as many (S for H) */
@@ -201,13 +214,13 @@ __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
 __device__ __forceinline__ uint32_t bam_unmapped_bytes(uint32_t L, uint32_t comment) { return BRX_BAM_CIGAR_AT + bam_bases_bytes(L) + 4u + comment; }
 
 /* bytes and primary record (BRX_SAM_UNMAPPED: none) of every read; with SA its records in the table too, as k_sam_size */
-template <uint32_t TAGS>
+template <uint32_t TAGS, bool F>
 __global__ void __launch_bounds__(64) k_bam_size(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t max_ops, uint32_t *len, uint32_t *best,
-                                                  uint32_t *n_rec) {
+                                                  uint32_t *n_rec, uint32_t fmt) {
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
     PafRead R; R.at = 0; R.best = 0; R.top = 0; R.n_rec = 0; R.frag = nullptr;
-    BamCount<TAGS> k_; k_.A.tab = nullptr; k_.A.n = 0; k_.A.sum = 0; k_.out = nullptr; k_.surplus = 0; k_.max_ops = max_ops; k_.M = sam_of(s, nullptr, arena); k_.T.fwd = k_.T.rev = 0;
+    BamCount<TAGS, F> k_; k_.fmt = F ? fmt : 0u; k_.A.tab = nullptr; k_.A.n = 0; k_.A.sum = 0; k_.out = nullptr; k_.surplus = 0; k_.max_ops = max_ops; k_.M = sam_of(s, nullptr, arena); k_.T.fwd = k_.T.rev = 0;
     if (paf_has_records(s)) paf_read(k_, d, s, r, segs, arena, R);
     uint32_t bytes = (uint32_t)R.at + k_.surplus, top = R.top;
     if (R.n_rec == 0) { top = BRX_SAM_UNMAPPED; bytes = s.rec_len ? bam_unmapped_bytes(s.seq_len, sam_comment(k_)) : 0u; }
@@ -219,17 +232,17 @@ __global__ void __launch_bounds__(64) k_bam_size(BrxDev d, const RS *rs, const P
     if (lane_id() == 0) { len[r] = bytes; best[r] = top; }
 }
 
-template <uint32_t TAGS>
+template <uint32_t TAGS, bool F>
 __global__ void __launch_bounds__(64) k_bam_write(BrxDev d, const RS *rs, const PSeg *segs, const PPiece *pieces, const uint8_t *arena, uint32_t max_ops,
                                                    const uint64_t *off, const uint32_t *best, uint8_t *out, const uint8_t *Fbuf,
-                                                   const uint64_t *rec_off, const SaRec *table) {
+                                                   const uint64_t *rec_off, const SaRec *table, uint32_t fmt) {
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
     if (s.rec_len == 0) return;
-    BamWrite<TAGS> w; w.A.tab = nullptr; w.A.n = 0; w.A.sum = 0; w.out = out; w.max_ops = max_ops; w.M = sam_of(s, pieces, arena); w.T = bam_nibbles(d);
+    BamWrite<TAGS, F> w; w.fmt = F ? fmt : 0u; w.A.tab = nullptr; w.A.n = 0; w.A.sum = 0; w.out = out; w.max_ops = max_ops; w.M = sam_of(s, pieces, arena); w.T = bam_nibbles(d);
     if (best[r] != BRX_SAM_UNMAPPED) {
         PafRead R; R.at = off[r]; R.best = best[r]; R.frag = nullptr;
-        if (TAGS & BRX_TAG_MD) R.frag = Fbuf + s.F_off;
+        if ((TAGS & BRX_TAG_MD) || F) R.frag = Fbuf + s.F_off;
         if (TAGS & BRX_TAG_SA) w.A = sa_read_of(table, rec_off, r);
         paf_read(w, d, s, r, segs, arena, R);
         return;

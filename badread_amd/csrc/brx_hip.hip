@@ -1276,10 +1276,12 @@ extern "C" int brx_bgzf_device(brx_ctx *c, const void *d_in, size_t n_bytes, voi
 enum { TRUTH_PAF = 0, TRUTH_SAM = 1, TRUTH_BAM = 2 };
 /* one instantiation of the SAM / BAM kernels per set of tags: 0 is the untagged code, nothing of the tags in its column loops */
 #define TAGGED(tags, LAUNCH) do { switch (tags) { case 0: { LAUNCH(0u); } break; case 1: { LAUNCH(1u); } break; case 2: { LAUNCH(2u); } break; default: { LAUNCH(3u); } break; } } while (0)
-static int emit_truth(brx_ctx *c, int kind, uint32_t tags, uint32_t max_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+static int emit_truth(brx_ctx *c, int kind, uint32_t fmt, uint32_t tags, uint32_t max_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
     if (!c || !out_bytes) return BRX_E_ARG;
     *out_bytes = 0;
     if (tags & ~(uint32_t)(BRX_TAG_MD | BRX_TAG_SA)) return fail(c, BRX_E_ARG, "truth tags %#x: only BRX_TAG_MD | BRX_TAG_SA", tags);
+    if ((fmt & ~(uint32_t)(BRX_FMT_EQX | BRX_FMT_CS | BRX_FMT_CS_LONG)) || (fmt & (BRX_FMT_CS | BRX_FMT_CS_LONG)) == BRX_FMT_CS_LONG)
+        return fail(c, BRX_E_ARG, "truth format %#x: BRX_FMT_EQX | BRX_FMT_CS | BRX_FMT_CS_LONG, the last only with BRX_FMT_CS", fmt);
     if (!c->paf_valid) return fail(c, BRX_E_STATE, "no simulate batch on this context to emit truth alignments for");
     hipStream_t st = (hipStream_t)hip_stream;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1299,13 +1301,25 @@ static int emit_truth(brx_ctx *c, int kind, uint32_t tags, uint32_t max_ops, uin
     uint64_t *off = (uint64_t *)(c->d_paf + off_at), *rec_off = (uint64_t *)(c->d_paf + recoff_at);
     const uint8_t *arena = (const uint8_t *)c->scratch;
     const bool sam = kind == TRUTH_SAM, bam = kind == TRUTH_BAM, sa = (tags & BRX_TAG_SA) != 0;
-#define BAM_SIZE(T) hipLaunchKernelGGL((k_bam_size<T>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, max_ops, len, best, n_rec)
-#define SAM_SIZE(T) hipLaunchKernelGGL((k_sam_size<T>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best, n_rec)
-    if (n && bam) TAGGED(tags, BAM_SIZE);
+    /* and two per set of tags: without format bits (the code of brx_emit_*_tags), and with them as a value of the grid's */
+#define BAM_SIZE_F(T, F) hipLaunchKernelGGL((k_bam_size<T, F>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, max_ops, len, best, n_rec, fmt)
+#define SAM_SIZE_F(T, F) hipLaunchKernelGGL((k_sam_size<T, F>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best, n_rec, fmt)
+#define BAM_SIZE(T) BAM_SIZE_F(T, false)
+#define SAM_SIZE(T) SAM_SIZE_F(T, false)
+#define BAM_SIZE_FMT(T) BAM_SIZE_F(T, true)
+#define SAM_SIZE_FMT(T) SAM_SIZE_F(T, true)
+    if (n && bam && fmt) TAGGED(tags, BAM_SIZE_FMT);
+    else if (n && bam) TAGGED(tags, BAM_SIZE);
+    else if (n && sam && fmt) TAGGED(tags, SAM_SIZE_FMT);
     else if (n && sam) TAGGED(tags, SAM_SIZE);
+    else if (n && fmt) hipLaunchKernelGGL(k_paf_size_fmt, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, fmt, len, best);
     else if (n) hipLaunchKernelGGL(k_paf_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best);
+#undef BAM_SIZE_F
+#undef SAM_SIZE_F
 #undef BAM_SIZE
 #undef SAM_SIZE
+#undef BAM_SIZE_FMT
+#undef SAM_SIZE_FMT
     if (sam || bam) hipLaunchKernelGGL(k_sam_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
     else hipLaunchKernelGGL(k_paf_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
     if (sa) hipLaunchKernelGGL(k_sam_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)n_rec, rec_off);
@@ -1327,38 +1341,61 @@ static int emit_truth(brx_ctx *c, int kind, uint32_t tags, uint32_t max_ops, uin
     }
     SaRec *table = (SaRec *)c->d_sa;
     if (n && total && sa_recs) hipLaunchKernelGGL(k_sa_fill, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, (const uint64_t *)rec_off, table);
-#define BAM_WRITE(T) hipLaunchKernelGGL((k_bam_write<T>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf, \
-                                        max_ops, (const uint64_t *)off, (const uint32_t *)best, d_out, c->paf_frags, (const uint64_t *)rec_off, (const SaRec *)table)
-#define SAM_WRITE(T) hipLaunchKernelGGL((k_sam_write<T>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf, \
-                                        (const uint64_t *)off, (const uint32_t *)best, d_out, c->paf_frags, (const uint64_t *)rec_off, (const SaRec *)table)
-    if (n && total && bam) TAGGED(tags, BAM_WRITE);
+#define BAM_WRITE_F(T, F) hipLaunchKernelGGL((k_bam_write<T, F>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf, \
+                                        max_ops, (const uint64_t *)off, (const uint32_t *)best, d_out, c->paf_frags, (const uint64_t *)rec_off, (const SaRec *)table, fmt)
+#define SAM_WRITE_F(T, F) hipLaunchKernelGGL((k_sam_write<T, F>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf, \
+                                        (const uint64_t *)off, (const uint32_t *)best, d_out, c->paf_frags, (const uint64_t *)rec_off, (const SaRec *)table, fmt)
+#define BAM_WRITE(T) BAM_WRITE_F(T, false)
+#define SAM_WRITE(T) SAM_WRITE_F(T, false)
+#define BAM_WRITE_FMT(T) BAM_WRITE_F(T, true)
+#define SAM_WRITE_FMT(T) SAM_WRITE_F(T, true)
+    if (n && total && bam && fmt) TAGGED(tags, BAM_WRITE_FMT);
+    else if (n && total && bam) TAGGED(tags, BAM_WRITE);
+    else if (n && total && sam && fmt) TAGGED(tags, SAM_WRITE_FMT);
     else if (n && total && sam) TAGGED(tags, SAM_WRITE);
+    else if (n && total && fmt) hipLaunchKernelGGL(k_paf_write_fmt, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, c->paf_seqbuf, c->paf_frags, fmt,
+                                                   (const uint64_t *)off, (const uint32_t *)best, d_out);
     else if (n && total) hipLaunchKernelGGL(k_paf_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena,
                                             (const uint64_t *)off, (const uint32_t *)best, d_out);
+#undef BAM_WRITE_F
+#undef SAM_WRITE_F
 #undef BAM_WRITE
 #undef SAM_WRITE
+#undef BAM_WRITE_FMT
+#undef SAM_WRITE_FMT
     if (d_read_off) HIPCHK(c, hipMemcpyAsync(d_read_off, c->h_paf + off_at, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
     { int rcw = wait_stream(c, st, bam ? "k_bam_write" : sam ? "k_sam_write" : "k_paf_write"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
     *out_bytes = (size_t)total;
     return BRX_OK;
 }
-extern "C" int brx_emit_paf(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return emit_truth(c, TRUTH_PAF, 0, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+extern "C" int brx_emit_paf_fmt(brx_ctx *c, uint32_t fmt, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+    return emit_truth(c, TRUTH_PAF, fmt, 0, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
 }
-extern "C" int brx_emit_sam_tags(brx_ctx *c, uint32_t tags, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return emit_truth(c, TRUTH_SAM, tags, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+extern "C" int brx_emit_sam_fmt(brx_ctx *c, uint32_t fmt, uint32_t tags, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+    return emit_truth(c, TRUTH_SAM, fmt, tags, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
 }
-extern "C" int brx_emit_sam(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return brx_emit_sam_tags(c, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
-}
-extern "C" int brx_emit_bam_tags(brx_ctx *c, uint32_t tags, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes,
-                                 void *hip_stream) {
+extern "C" int brx_emit_bam_fmt(brx_ctx *c, uint32_t fmt, uint32_t tags, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off,
+                                size_t *out_bytes, void *hip_stream) {
     if (!c || !out_bytes) return BRX_E_ARG;
     if (max_cigar_ops == 0) max_cigar_ops = 65535;
     if (max_cigar_ops < 2 || max_cigar_ops > 65535) return fail(c, BRX_E_ARG, "brx_emit_bam: max_cigar_ops %u (2..65535, or 0 for 65535)", max_cigar_ops);
-    return emit_truth(c, TRUTH_BAM, tags, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+    return emit_truth(c, TRUTH_BAM, fmt, tags, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+}
+/* the functions without formats: fmt = 0 */
+extern "C" int brx_emit_paf(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+    return brx_emit_paf_fmt(c, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+}
+extern "C" int brx_emit_sam_tags(brx_ctx *c, uint32_t tags, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+    return brx_emit_sam_fmt(c, 0, tags, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+}
+extern "C" int brx_emit_sam(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+    return brx_emit_sam_fmt(c, 0, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+}
+extern "C" int brx_emit_bam_tags(brx_ctx *c, uint32_t tags, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes,
+                                 void *hip_stream) {
+    return brx_emit_bam_fmt(c, 0, tags, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
 }
 extern "C" int brx_emit_bam(brx_ctx *c, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return brx_emit_bam_tags(c, 0, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+    return brx_emit_bam_fmt(c, 0, 0, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
 }

@@ -19,6 +19,11 @@
  *              '-' records mirror the runs, the convention of minimap2 that alignment.py undoes)
  * The same code sizes (PafCount) and writes (PafWrite): k_paf_size / k_paf_scan / k_paf_write, the pattern of
  * k_recsize / k_scan_rec / k_emit.  The walk hands every record to its sink (sink.record), so brx_sam.h walks the same records.
+ *
+ * brx_emit_paf_fmt (BRX_FMT_*): with BRX_FMT_EQX a CIGAR run is a run of one op instead of one class (template parameter EQX of the
+ * sweeps, paf_run), with BRX_FMT_CS a third sweep (cs_sweep) writes minimap2's cs:Z: behind AS:i:.  The sinks PafFmtCount / PafFmtWrite
+ * and the kernels k_paf_size_fmt / k_paf_write_fmt carry the bits as a value; PafCount / PafWrite and k_paf_size / k_paf_write hold
+ * nothing of them.  brx_sam.h and brx_bam.h use the same sweeps.
  */
 #ifndef BRX_PAF_H
 #define BRX_PAF_H
@@ -29,12 +34,17 @@
 __device__ __forceinline__ uint32_t paf_digits(uint32_t v) { uint32_t n = 1; while (v >= 10) { v /= 10; ++n; } return n; }
 __device__ __forceinline__ int paf_top(uint64_t bits) { return 63 - __builtin_clzll(bits); }     /* bits != 0 */
 __device__ __forceinline__ uint32_t paf_cls(uint32_t op) { return op <= 1 ? 0u : op; }              /* M (= or X), I, D */
+/* what a CIGAR run is a run of: the class, or with BRX_FMT_EQX the op itself (= X I D) */
+template <bool EQX> __device__ __forceinline__ uint32_t paf_run(uint32_t op) { return EQX ? op : paf_cls(op); }
+template <bool EQX> __device__ __forceinline__ uint8_t paf_letter(uint32_t op) {
+    return (uint8_t)(EQX ? (op == 0 ? '=' : op == 1 ? 'X' : op == 2 ? 'I' : 'D') : (op <= 1 ? 'M' : op == 2 ? 'I' : 'D'));
+}
 
 struct PafRec { uint32_t c0, c1, r0, f0; uint64_t key0; };      /* first / last M column, read index and origin of the first; f0: its index in the
-                                                                    padded fragment, kept only for a sink that asks (S::need_f0: MD:Z:, brx_sam.h) */
+                                                                    padded fragment, kept only for a sink that asks (S::need_f0: MD:Z:, brx_sam.h; cs:Z:) */
 struct PafRead {                                                 /* what a record needs of its read (uniform over the wave) */
     const uint8_t *ops; uint64_t read; uint32_t seq_len, start_trim;
-    const uint8_t *frag;             /* the padded fragment the read was aligned against (Fbuf + RS.F_off); set by the kernels that write MD:Z: */
+    const uint8_t *frag;             /* the padded fragment the read was aligned against (Fbuf + RS.F_off); set by the kernels that write MD:Z: or cs:Z: */
     uint32_t best;                   /* the primary record (writing sink: found by the sizing pass) */
     uint32_t n_rec, top, top_set; int64_t top_as; uint64_t at;      /* records so far, the first of the highest AS among them */
 };
@@ -43,13 +53,24 @@ struct PafShape { uint32_t cnt[4], text, runs; };                /* a record's c
 /* The sinks of the walk (paf_read): what is done with every record it closes.  brx_sam.h adds its own two. */
 template <class S> __device__ void paf_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q);
 struct PafCount {
-    static constexpr bool write = false, need_f0 = false; uint8_t *out;
+    static constexpr bool write = false, need_f0 = false, fmtd = false; uint8_t *out;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { paf_record(*this, d, R, q); }
 };
 struct PafWrite {
-    static constexpr bool write = true, need_f0 = false; uint8_t *out;
+    static constexpr bool write = true, need_f0 = false, fmtd = false; uint8_t *out;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { paf_record(*this, d, R, q); }
 };
+/* brx_emit_paf_fmt: the same two with BRX_FMT_* bits (fmt, uniform over the grid) and the read's kept bases for cs:Z: (seq) */
+struct PafFmtCount {
+    static constexpr bool write = false, need_f0 = true, fmtd = true; uint8_t *out; uint32_t fmt; const uint8_t *seq;
+    __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { paf_record(*this, d, R, q); }
+};
+struct PafFmtWrite {
+    static constexpr bool write = true, need_f0 = true, fmtd = true; uint8_t *out; uint32_t fmt; const uint8_t *seq;
+    __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { paf_record(*this, d, R, q); }
+};
+/* a sink's BRX_FMT_* bits: the constant 0 for the sinks without (fmtd = false), whose code holds nothing of the formats */
+template <class S> __device__ __forceinline__ uint32_t sink_fmt(const S &sink) { if constexpr (S::fmtd) return sink.fmt; else return 0u; }
 
 /* The header fields of a record (qname .. cg:Z:) and its tail (\tNM:i:..\tAS:i:..\n). */
 template <class B>
@@ -77,6 +98,7 @@ __device__ void paf_tail(B &b, uint32_t nm, int64_t as) { paf_tags(b, nm, as); b
 
 /* Sweep 1 over the record [q.c0, q.c1]: op counts, the CIGAR's text length and its number of runs.  A lane whose column ends a run (the next column
    is another class, or the record ends) owns that run's text: its decimal length and the letter.  Every lane calls it. */
+template <bool EQX>
 __device__ PafShape paf_shape(const PafRead &R, const PafRec &q) {
     const int lane = lane_id();
     const uint64_t below = (1ull << lane) - 1ull;
@@ -88,8 +110,8 @@ __device__ PafShape paf_shape(const PafRead &R, const PafRec &q) {
         const uint32_t op = in ? R.ops[c] : 0u;
         const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
         const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
-        const bool rs = in && (c == q.c0 || paf_cls(prev) != paf_cls(op));
-        const bool re = in && (c == q.c1 || paf_cls(next) != paf_cls(op));
+        const bool rs = in && (c == q.c0 || paf_run<EQX>(prev) != paf_run<EQX>(op));
+        const bool re = in && (c == q.c1 || paf_run<EQX>(next) != paf_run<EQX>(op));
         const uint64_t rmask = __ballot(rs);
         const uint64_t mine = rmask & (below | (1ull << lane));
         const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
@@ -104,6 +126,7 @@ __device__ PafShape paf_shape(const PafRead &R, const PafRec &q) {
 
 /* Sweep 2: every run's text at its place in cig[0, text); the prefix sum of the text lengths over the lanes gives it.  '-'
    records mirror the runs. */
+template <bool EQX>
 __device__ void paf_cigar(const PafRead &R, const PafRec &q, uint8_t *cig, uint32_t text, bool minus) {
     const int lane = lane_id();
     const uint64_t below = (1ull << lane) - 1ull;
@@ -114,8 +137,8 @@ __device__ void paf_cigar(const PafRead &R, const PafRec &q, uint8_t *cig, uint3
         const uint32_t op = in ? R.ops[c] : 0u;
         const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
         const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
-        const bool rs = in && (c == q.c0 || paf_cls(prev) != paf_cls(op));
-        const bool re = in && (c == q.c1 || paf_cls(next) != paf_cls(op));
+        const bool rs = in && (c == q.c0 || paf_run<EQX>(prev) != paf_run<EQX>(op));
+        const bool re = in && (c == q.c1 || paf_run<EQX>(next) != paf_run<EQX>(op));
         const uint64_t rmask = __ballot(rs);
         const uint64_t mine = rmask & (below | (1ull << lane));
         const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
@@ -127,12 +150,71 @@ __device__ void paf_cigar(const PafRead &R, const PafRec &q, uint8_t *cig, uint3
             uint8_t *p = cig + (minus ? text - fwd - t : fwd);
             uint32_t v = len;
             for (uint32_t x = t - 1; x-- > 0;) { p[x] = (uint8_t)('0' + v % 10); v /= 10; }
-            const uint32_t cl = paf_cls(op);
-            p[t - 1] = (uint8_t)(cl == 0 ? 'M' : cl == 2 ? 'I' : 'D');
+            p[t - 1] = paf_letter<EQX>(op);
         }
         done += wave_bcast_u32(incl, 63);
         if (rmask) run_start = b + (uint32_t)paf_top(rmask);
     }
+}
+
+/* ---- cs:Z: (BRX_FMT_CS) ----------------------------------------------------------------------------------------------------- */
+#define BRX_PAF_CS "\tcs:Z:"
+#define BRX_PAF_CS_LEN ((uint32_t)sizeof(BRX_PAF_CS) - 1u)
+
+/* The sweep over the record [q.c0, q.c1] for minimap2's cs.  Every column owns a piece of the value (possibly empty), the wave's prefix
+   sum places it:
+     =  short form: the LAST column of a run of n owns ":n" (n = its distance to the run's first column, found as paf_shape finds it: the
+        ballot of the run starts, carried across steps); long form: every column owns its reference base, the run's first one '=' before it
+     X  "*", the reference base, the read's base
+     I  the read's base; the run's first column '+' before it          D  the reference base; the run's first column '-' before it
+   Bases of X, I and D in lower case.  '-' records are mirrored piece by piece (a piece keeps its own order), the bases complemented, and
+   the '=' '+' '-' in front of a run goes to the run's LAST column, as '^' does in md_sweep.  The reference base is the fragment's
+   (R.frag at q.f0 + the target columns before the lane: MD's base), the read's base is seq[(q.r0 - start_trim) + the query columns before
+   the lane] (what SEQ holds).  WRITE = false only sizes: no fragment or sequence byte is read; it returns the value's length, which the
+   writing sweep is given.  Every lane calls it. */
+template <bool WRITE>
+__device__ uint32_t cs_sweep(const BrxDev &d, const PafRead &R, const PafRec &q, bool minus, bool lng, const uint8_t *seq, uint8_t *cs, uint32_t text) {
+    const int lane = lane_id();
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint32_t done = 0, run_start = q.c0, f_base = q.f0, r_base = q.r0 - R.start_trim;
+    for (uint32_t b = q.c0; b <= q.c1; b += 64) {
+        const uint32_t c = b + lane;
+        const bool in = c <= q.c1;
+        const uint32_t op = in ? R.ops[c] : 0u;
+        const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
+        const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
+        const bool rs = in && prev != op, re = in && next != op;
+        const bool lead = minus ? re : rs;
+        const uint64_t rmask = __ballot(rs);
+        const uint64_t mine = rmask & (below | (1ull << lane));
+        const uint32_t n = c - (mine ? b + (uint32_t)paf_top(mine) : run_start) + 1u;
+        uint32_t t = 0;
+        if (in) t = op == 1u ? 3u : (op == 0u && !lng) ? (re ? 1u + paf_digits(n) : 0u) : 1u + (lead ? 1u : 0u);
+        if (!WRITE) done += wave_sum(t);
+        else {
+            const uint64_t tm = __ballot(in && op != 2u), qm = __ballot(in && op != 3u);
+            const uint32_t incl = wave_incl_scan(t);
+            if (t) {
+                uint8_t *p = cs + (minus ? text - (done + incl) : done + incl - t);
+                uint8_t rb = 0, qb = 0;
+                if (op != 2u) { const uint32_t code = R.frag[f_base + (uint32_t)__popcll(tm & below)] & 15u; rb = d.ref.sym[minus ? d.ref.comp[code] & 15u : code]; }
+                if (op != 3u && op != 0u) { const uint32_t code = seq[r_base + (uint32_t)__popcll(qm & below)] & 15u; qb = d.ref.sym[minus ? d.ref.comp[code] & 15u : code]; }
+                if (op == 1u) { p[0] = '*'; p[1] = (uint8_t)(rb | 0x20u); p[2] = (uint8_t)(qb | 0x20u); }
+                else if (op == 0u && !lng) {
+                    p[0] = ':';
+                    uint32_t v = n;
+                    for (uint32_t x = t - 1u; x > 0; --x) { p[x] = (uint8_t)('0' + v % 10); v /= 10; }
+                } else {
+                    if (lead) p[0] = (uint8_t)(op == 0u ? '=' : op == 2u ? '+' : '-');
+                    p[t - 1u] = op == 0u ? rb : (uint8_t)((op == 2u ? qb : rb) | 0x20u);
+                }
+            }
+            done += wave_bcast_u32(incl, 63);
+            f_base += (uint32_t)__popcll(tm); r_base += (uint32_t)__popcll(qm);
+        }
+        if (rmask) run_start = b + (uint32_t)paf_top(rmask);
+    }
+    return WRITE ? text : done;
 }
 
 /* Counts the record in; true when it is the read's best so far: the first of the highest AS becomes the primary. */
@@ -146,7 +228,9 @@ __device__ __forceinline__ bool paf_rank(PafRead &R, int64_t as) {
 /* One record [q.c0, q.c1] of the read: sized, and written when S writes.  Every lane calls it (wave-uniform arguments). */
 template <class S>
 __device__ void paf_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q) {
-    const PafShape sh = paf_shape(R, q);
+    const uint32_t fmt = sink_fmt(sink);
+    const bool eqx = (fmt & BRX_FMT_EQX) != 0, minus = ((q.key0 >> 32) & 1u) != 0;
+    const PafShape sh = eqx ? paf_shape<true>(R, q) : paf_shape<false>(R, q);
     const uint32_t *cnt = sh.cnt, text = sh.text;
     const uint32_t cols = q.c1 - q.c0 + 1u;
     const uint32_t nm = cnt[1] + cnt[2] + cnt[3];
@@ -157,18 +241,27 @@ __device__ void paf_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
     CountSink hc; hc.n = 0;
     paf_head(hc, d, R, q, qcols, tspan, cnt[0], cols, primary);
     CountSink tc; tc.n = 0;
-    paf_tail(tc, nm, as);
+    paf_tags(tc, nm, as);
+    uint32_t cs_text = 0, cs_len = 0;
+    if constexpr (S::fmtd) if (fmt & BRX_FMT_CS) {
+        cs_text = cs_sweep<false>(d, R, q, minus, (fmt & BRX_FMT_CS_LONG) != 0, nullptr, nullptr, 0u);
+        cs_len = BRX_PAF_CS_LEN + cs_text;
+    }
     if (S::write) {
         uint8_t *o = sink.out + R.at;
         if (lane_id() == 0) {
             ByteSink h; h.p = o; h.n = 0;
             paf_head(h, d, R, q, qcols, tspan, cnt[0], cols, primary);
             ByteSink tl; tl.p = o + hc.n + text; tl.n = 0;
-            paf_tail(tl, nm, as);
+            paf_tags(tl, nm, as);
+            if (cs_len) { put_str(tl, BRX_PAF_CS); tl.n += cs_text; }                 /* the value is the wave's, below */
+            tl.put('\n');
         }
-        paf_cigar(R, q, o + hc.n, text, ((q.key0 >> 32) & 1u) != 0);
+        if (eqx) paf_cigar<true>(R, q, o + hc.n, text, minus); else paf_cigar<false>(R, q, o + hc.n, text, minus);
+        if constexpr (S::fmtd) if (cs_len)
+            cs_sweep<true>(d, R, q, minus, (fmt & BRX_FMT_CS_LONG) != 0, sink.seq, o + hc.n + text + tc.n + BRX_PAF_CS_LEN, cs_text);
     }
-    R.at += hc.n + text + tc.n;
+    R.at += hc.n + text + tc.n + cs_len + 1u;
 }
 
 /* Every record of read r, in column order (= increasing qstart); R.at advances by the read's PAF bytes, R.top = its primary. */
@@ -279,6 +372,26 @@ __global__ void __launch_bounds__(64) k_paf_write(BrxDev d, const RS *rs, const 
     if (!paf_has_records(s)) return;
     PafRead R; R.at = off[r]; R.best = best[r];
     PafWrite w; w.out = out;
+    paf_read(w, d, s, r, segs, arena, R);
+}
+
+/* brx_emit_paf_fmt with fmt != 0: the two kernels above with the format bits; the writing one is given the fragments (Fbuf) and the
+   reads' sequences (seqbuf, where k_emit read them) for cs:Z: */
+__global__ void __launch_bounds__(64) k_paf_size_fmt(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t fmt, uint32_t *len, uint32_t *best) {
+    const uint32_t r = blockIdx.x;
+    const RS s = rs[r];
+    PafRead R; R.at = 0; R.best = 0; R.top = 0; R.frag = nullptr;
+    if (paf_has_records(s)) { PafFmtCount k_; k_.out = nullptr; k_.fmt = fmt; k_.seq = nullptr; paf_read(k_, d, s, r, segs, arena, R); }
+    if (lane_id() == 0) { len[r] = (uint32_t)R.at; best[r] = R.top; }
+}
+
+__global__ void __launch_bounds__(64) k_paf_write_fmt(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, const uint8_t *seqbuf, const uint8_t *Fbuf,
+                                                       uint32_t fmt, const uint64_t *off, const uint32_t *best, uint8_t *out) {
+    const uint32_t r = blockIdx.x;
+    const RS s = rs[r];
+    if (!paf_has_records(s)) return;
+    PafRead R; R.at = off[r]; R.best = best[r]; R.frag = Fbuf + s.F_off;
+    PafFmtWrite w; w.out = out; w.fmt = fmt; w.seq = seqbuf + s.seq_off + s.start_trim;           /* as k_emit reads them */
     paf_read(w, d, s, r, segs, arena, R);
 }
 

@@ -17,6 +17,9 @@
  * read; lane 0 writes the fixed fields, the wave places the CIGAR runs and copies SEQ and QUAL 64 bytes per step (contiguous
  * stores; on '-' lines the loads run backwards).
  *
+ * brx_emit_sam_fmt adds =/X CIGAR runs and cs:Z: (BRX_FMT_*; template parameter F of the sinks and kernels: with F the bits are a value
+ * uniform over the grid, without it the code holds nothing of them).  The runs are paf_shape's and paf_cigar's, cs is brx_paf.h's cs_sweep.
+ *
  * brx_emit_sam_tags adds MD:Z: and SA:Z: behind AS:i: (template parameter TAGS of the sinks and kernels; TAGS = 0 is the code above).
  *   MD  a third sweep over the record's columns (md_sweep): every X column and every D column owns a piece of the text, the wave's
  *       prefix sum places it; the number in front of an item is the count of '=' columns since the item before it (ballot
@@ -158,9 +161,9 @@ __device__ SaRec sa_rec_of(const BrxDev &d, const PafRead &R, const PafRec &q, c
 
 /* the sink of k_sa_fill: record i of the read goes to tab[i] */
 struct SaFill {
-    static constexpr bool write = false, need_f0 = false; SaRec *tab;
+    static constexpr bool write = false, need_f0 = false, fmtd = false; SaRec *tab;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) {
-        const PafShape sh = paf_shape(R, q);
+        const PafShape sh = paf_shape<false>(R, q);                       /* the compact CIGAR takes the op counts alone */
         const SaRec e = sa_rec_of(d, R, q, sh);
         if (lane_id() == 0) tab[R.n_rec] = e;
         R.n_rec += 1;
@@ -196,27 +199,30 @@ __device__ void sa_write(const BrxDev &d, const SaRead &A, uint32_t i, uint32_t 
 }
 
 template <class S> __device__ void sam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q);
-template <uint32_t TAGS> struct SamCount {
-    static constexpr bool write = false, need_f0 = (TAGS & BRX_TAG_MD) != 0; static constexpr uint32_t tags = TAGS;
-    uint8_t *out; SamRead M; uint32_t surplus; SaRead A;             /* A.sum: the elements' lengths of the records so far */
+/* F: the sink carries BRX_FMT_* bits (fmt, uniform over the grid); F = false is the code without them */
+template <uint32_t TAGS, bool F> struct SamCount {
+    static constexpr bool write = false, fmtd = F, need_f0 = (TAGS & BRX_TAG_MD) != 0 || F; static constexpr uint32_t tags = TAGS;
+    uint8_t *out; SamRead M; uint32_t surplus, fmt; SaRead A;        /* A.sum: the elements' lengths of the records so far */
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { sam_record(*this, d, R, q); }
 };
-template <uint32_t TAGS> struct SamWrite {
-    static constexpr bool write = true, need_f0 = (TAGS & BRX_TAG_MD) != 0; static constexpr uint32_t tags = TAGS;
-    uint8_t *out; SamRead M; SaRead A;
+template <uint32_t TAGS, bool F> struct SamWrite {
+    static constexpr bool write = true, fmtd = F, need_f0 = (TAGS & BRX_TAG_MD) != 0 || F; static constexpr uint32_t tags = TAGS;
+    uint8_t *out; SamRead M; uint32_t fmt; SaRead A;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { sam_record(*this, d, R, q); }
 };
 /* the comment's length: the FASTQ header is '@', the name, a blank, the comment and a newline (RS.hdr_len, k_recsize) */
 template <class S> __device__ __forceinline__ uint32_t sam_comment(const S &sink) { return sink.M.s->hdr_len - (BRX_SAM_NAME + 3u); }
-template <uint32_t TAGS> __device__ __forceinline__ void sink_surplus(SamCount<TAGS> &k, uint32_t v) { k.surplus = v; }
-template <uint32_t TAGS> __device__ __forceinline__ void sink_surplus(SamWrite<TAGS> &, uint32_t) {}
+template <uint32_t TAGS, bool F> __device__ __forceinline__ void sink_surplus(SamCount<TAGS, F> &k, uint32_t v) { k.surplus = v; }
+template <uint32_t TAGS, bool F> __device__ __forceinline__ void sink_surplus(SamWrite<TAGS, F> &, uint32_t) {}
 
 
 /* One record of the read as a SAM line: sized (as a supplementary line; the primary's surplus goes with the best AS), or
    written.  Every lane calls it (wave-uniform arguments). */
 template <class S>
 __device__ void sam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q) {
-    const PafShape sh = paf_shape(R, q);
+    const uint32_t fmt = sink_fmt(sink);
+    const bool eqx = (fmt & BRX_FMT_EQX) != 0;
+    const PafShape sh = eqx ? paf_shape<true>(R, q) : paf_shape<false>(R, q);
     const uint32_t nm = sh.cnt[1] + sh.cnt[2] + sh.cnt[3];
     const int64_t as = (int64_t)sh.cnt[0] - (int64_t)nm;
     const uint32_t qcols = sh.cnt[0] + sh.cnt[1] + sh.cnt[2], tspan = sh.cnt[0] + sh.cnt[1] + sh.cnt[3];
@@ -234,6 +240,11 @@ __device__ void sam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
         if (!S::write) sink.A.sum += sa_rec_of(d, R, q, sh).len;
         else if (sink.A.n) sa_len = BRX_SAM_LEN(BRX_SAM_SA) + sink.A.sum - sink.A.tab[line].len;
     }
+    uint32_t cs_text = 0, cs_len = 0;                                                 /* cs:Z: between MD and SA */
+    if constexpr (S::fmtd) if (fmt & BRX_FMT_CS) {
+        cs_text = cs_sweep<false>(d, R, q, minus, (fmt & BRX_FMT_CS_LONG) != 0, nullptr, nullptr, 0u);
+        cs_len = BRX_PAF_CS_LEN + cs_text;
+    }
     CountSink hc; hc.n = 0;
     sam_head(hc, d, R, q, tspan, primary);
     CountSink lc; lc.n = 0; sam_clip(lc, left, primary);
@@ -242,7 +253,7 @@ __device__ void sam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
     const uint32_t comment = sam_comment(sink);
     const uint32_t bases = primary ? L : qcols;
     const uint32_t cig_at = hc.n + lc.n, seq_at = cig_at + sh.text + rc.n + BRX_SAM_LEN(BRX_SAM_MATE), tag_at = seq_at + 2u * bases + 1u;
-    const uint32_t bytes = tag_at + tc.n + md_len + sa_len + (primary ? BRX_SAM_LEN(BRX_SAM_CO) + comment : 0u) + 1u;
+    const uint32_t bytes = tag_at + tc.n + md_len + cs_len + sa_len + (primary ? BRX_SAM_LEN(BRX_SAM_CO) + comment : 0u) + 1u;
     if (S::write) {
         uint8_t *o = sink.out + R.at;
         if (lane_id() == 0) {
@@ -253,13 +264,16 @@ __device__ void sam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
             ByteSink t; t.p = o + tag_at; t.n = 0;
             paf_tags(t, nm, as);
             if (md_len) { put_str(t, BRX_SAM_MD); t.n += md.text; }            /* the values are the wave's, below */
+            if (cs_len) { put_str(t, BRX_PAF_CS); t.n += cs_text; }
             if (sa_len) { put_str(t, BRX_SAM_SA); t.n += sa_len - BRX_SAM_LEN(BRX_SAM_SA); }
             if (primary) { put_str(t, BRX_SAM_CO); put_comment(t, d, *sink.M.s, sink.M.pieces); }
             t.put('\n');
         }
         if (md_len) md_sweep<true>(d, R, q, minus, o + tag_at + tc.n + BRX_SAM_LEN(BRX_SAM_MD), md);
-        if (sa_len) sa_write(d, sink.A, line, R.best, o + tag_at + tc.n + md_len + BRX_SAM_LEN(BRX_SAM_SA));
-        paf_cigar(R, q, o + cig_at, sh.text, minus);
+        if constexpr (S::fmtd) if (cs_len)
+            cs_sweep<true>(d, R, q, minus, (fmt & BRX_FMT_CS_LONG) != 0, sink.M.seq, o + tag_at + tc.n + md_len + BRX_PAF_CS_LEN, cs_text);
+        if (sa_len) sa_write(d, sink.A, line, R.best, o + tag_at + tc.n + md_len + cs_len + BRX_SAM_LEN(BRX_SAM_SA));
+        if (eqx) paf_cigar<true>(R, q, o + cig_at, sh.text, minus); else paf_cigar<false>(R, q, o + cig_at, sh.text, minus);
         sam_bases(d, sink.M, o + seq_at, primary ? 0u : qs, primary ? L : qe, minus);
     } else if (top) {
         /* the same record as the primary: FLAG loses its 2048 (4 digits -> "0" or "16"), SEQ and QUAL are the whole read, CO:Z: */
@@ -281,13 +295,13 @@ __device__ __forceinline__ SamRead sam_of(const RS &s, const PPiece *pieces, con
 }
 
 /* bytes and primary record (BRX_SAM_UNMAPPED: none) of every read; with SA its records in the table too (n_rec: 0 below two) */
-template <uint32_t TAGS>
+template <uint32_t TAGS, bool F>
 __global__ void __launch_bounds__(64) k_sam_size(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t *len, uint32_t *best,
-                                                  uint32_t *n_rec) {
+                                                  uint32_t *n_rec, uint32_t fmt) {
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
     PafRead R; R.at = 0; R.best = 0; R.top = 0; R.n_rec = 0; R.frag = nullptr;
-    SamCount<TAGS> k_; k_.out = nullptr; k_.surplus = 0; k_.M = sam_of(s, nullptr, arena); k_.A.tab = nullptr; k_.A.n = 0; k_.A.sum = 0;
+    SamCount<TAGS, F> k_; k_.out = nullptr; k_.surplus = 0; k_.fmt = F ? fmt : 0u; k_.M = sam_of(s, nullptr, arena); k_.A.tab = nullptr; k_.A.n = 0; k_.A.sum = 0;
     if (paf_has_records(s)) paf_read(k_, d, s, r, segs, arena, R);
     uint32_t bytes = (uint32_t)R.at + k_.surplus, top = R.top;
     if (R.n_rec == 0) { top = BRX_SAM_UNMAPPED; bytes = s.rec_len ? sam_unmapped_bytes(s.seq_len, sam_comment(k_)) : 0u; }
@@ -328,17 +342,17 @@ __global__ void __launch_bounds__(64) k_sam_scan(uint32_t n_reads, const uint32_
     if (lane == 0) off[n_reads] = run;
 }
 
-template <uint32_t TAGS>
+template <uint32_t TAGS, bool F>
 __global__ void __launch_bounds__(64) k_sam_write(BrxDev d, const RS *rs, const PSeg *segs, const PPiece *pieces, const uint8_t *arena,
                                                    const uint64_t *off, const uint32_t *best, uint8_t *out, const uint8_t *Fbuf,
-                                                   const uint64_t *rec_off, const SaRec *table) {
+                                                   const uint64_t *rec_off, const SaRec *table, uint32_t fmt) {
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
     if (s.rec_len == 0) return;
-    SamWrite<TAGS> w; w.out = out; w.M = sam_of(s, pieces, arena); w.A.tab = nullptr; w.A.n = 0; w.A.sum = 0;
+    SamWrite<TAGS, F> w; w.fmt = F ? fmt : 0u; w.out = out; w.M = sam_of(s, pieces, arena); w.A.tab = nullptr; w.A.n = 0; w.A.sum = 0;
     if (best[r] != BRX_SAM_UNMAPPED) {
         PafRead R; R.at = off[r]; R.best = best[r]; R.frag = nullptr;
-        if (TAGS & BRX_TAG_MD) R.frag = Fbuf + s.F_off;
+        if ((TAGS & BRX_TAG_MD) || F) R.frag = Fbuf + s.F_off;
         if (TAGS & BRX_TAG_SA) w.A = sa_read_of(table, rec_off, r);
         paf_read(w, d, s, r, segs, arena, R);
         return;

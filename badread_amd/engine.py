@@ -93,6 +93,20 @@ SA_SHARE = 0.012
 
 def tag_share(tags):
     return (MD_SHARE if tags & TAG_MD else 0.0) + (SA_SHARE if tags & TAG_SA else 0.0)
+# --truth-eqx / --truth-cs: what =/X CIGAR runs and cs:Z: add to a batch's PAF, SAM or BAM records, per FASTQ byte and per file
+# (measured on configs[3], profiles/truth_cs.md: EQX 0.0372-0.0375 as text and 0.0697-0.0702 as BAM words, short cs 0.1162-0.1172,
+# long cs 0.5516-0.5523; shipped: the maximum plus about 15 % of itself.  Short cs grows with the error rate like MD, long cs is
+# about one byte per aligned base, and E_OUTPUT's retry is behind all of them)
+FMT_EQX, FMT_CS, FMT_CS_LONG = 1, 2, 4  # include/brx.h: BRX_FMT_EQX, BRX_FMT_CS, BRX_FMT_CS_LONG
+EQX_SHARE = dict(paf=0.043, sam=0.043, bam=0.081)
+CS_SHORT_SHARE = dict(paf=0.135, sam=0.135, bam=0.135)
+CS_LONG_SHARE = dict(paf=0.635, sam=0.635, bam=0.635)
+
+
+def fmt_share(fmt, kind):
+    """What the format bits add to the file `kind` ('paf', 'sam' or 'bam'), per FASTQ byte."""
+    cs = (CS_LONG_SHARE if fmt & FMT_CS_LONG else CS_SHORT_SHARE)[kind] if fmt & FMT_CS else 0.0
+    return (EQX_SHARE[kind] if fmt & FMT_EQX else 0.0) + cs
 E_SCRATCH, E_OUTPUT, E_NOFRAG = -3, -4, -5
 STAGE_NAMES = ('plan', 'build', 'mutate', 'scan', 'final', 'emit', 'align1', 'qscore')
 # kernel classes of brx_last_kernel_stats (include/brx.h: BRX_KERN_*), with the names a rocprofv3 kernel trace shows
@@ -313,6 +327,9 @@ def bind_library(lib):
     lib.brx_emit_sam_tags.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + list(lib.brx_emit_paf.argtypes[1:])
     lib.brx_emit_bam_tags.restype = ctypes.c_int
     lib.brx_emit_bam_tags.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32] + list(lib.brx_emit_paf.argtypes[1:])
+    for name, extra in (('brx_emit_paf_fmt', 1), ('brx_emit_sam_fmt', 2), ('brx_emit_bam_fmt', 3)):       # fmt; tags; max_cigar_ops
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [ctypes.c_void_p] + [ctypes.c_uint32] * extra + list(lib.brx_emit_paf.argtypes[1:])
     lib.brx_bgzf_device_bound.restype = ctypes.c_size_t
     lib.brx_bgzf_device_bound.argtypes = [ctypes.c_size_t]
     lib.brx_bgzf_device_scratch.restype = ctypes.c_size_t
@@ -560,24 +577,35 @@ class HipEngine(EngineBase):
         stats = self._stats[:n_reads * READ_STATS_DTYPE.itemsize].cpu().numpy().view(READ_STATS_DTYPE)
         return self._out[:nbytes], stats
 
-    def emit_paf_device(self, n_reads):
+    def emit_paf_device(self, n_reads, fmt=0):
         """Truth alignments (PAF text, include/brx.h brx_emit_paf) of the last simulate_batch(_device) of this engine, which had
         `n_reads` reads: (device uint8 tensor of the records in read order, numpy uint64 offsets of each read's records, n_reads + 1
-        entries).  The tensor is a fresh one: the engine may take its next batch at once."""
-        return self._emit_truth(self.lib.brx_emit_paf, PAF_SHARE, n_reads)
+        entries).  The tensor is a fresh one: the engine may take its next batch at once.  `fmt`: FMT_EQX | FMT_CS | FMT_CS_LONG, =/X
+        runs in cg:Z: and a cs:Z: behind AS (brx_emit_paf_fmt)."""
+        if not fmt:
+            return self._emit_truth(self.lib.brx_emit_paf, PAF_SHARE, n_reads)
+        emit = lambda ctx, *rest: self.lib.brx_emit_paf_fmt(ctx, int(fmt), *rest)
+        return self._emit_truth(emit, PAF_SHARE + fmt_share(fmt, 'paf'), n_reads)
 
-    def emit_sam_device(self, n_reads, tags=0):
+    def emit_sam_device(self, n_reads, tags=0, fmt=0):
         """The same truth as SAM records (include/brx.h brx_emit_sam; no header), with emit_paf_device's arguments and results.
-        Both may be called for one batch, in either order.  `tags`: TAG_MD | TAG_SA adds MD:Z: / SA:Z: (brx_emit_sam_tags)."""
-        emit = lambda ctx, *rest: self.lib.brx_emit_sam_tags(ctx, int(tags), *rest)
-        return self._emit_truth(emit, SAM_SHARE + tag_share(tags), n_reads)
+        Both may be called for one batch, in either order.  `tags`: TAG_MD | TAG_SA adds MD:Z: / SA:Z: (brx_emit_sam_tags); `fmt` as for
+        emit_paf_device (brx_emit_sam_fmt)."""
+        if not fmt:
+            emit = lambda ctx, *rest: self.lib.brx_emit_sam_tags(ctx, int(tags), *rest)
+        else:
+            emit = lambda ctx, *rest: self.lib.brx_emit_sam_fmt(ctx, int(fmt), int(tags), *rest)
+        return self._emit_truth(emit, SAM_SHARE + tag_share(tags) + fmt_share(fmt, 'sam'), n_reads)
 
-    def emit_bam_device(self, n_reads, max_cigar_ops=65535, tags=0):
+    def emit_bam_device(self, n_reads, max_cigar_ops=65535, tags=0, fmt=0):
         """The same truth as uncompressed BAM records (include/brx.h brx_emit_bam; no header), one per SAM line, with
         emit_paf_device's arguments and results.  A record with more than `max_cigar_ops` CIGAR operations takes the CG:B:I form;
-        `tags` as for emit_sam_device (brx_emit_bam_tags)."""
-        emit = lambda ctx, *rest: self.lib.brx_emit_bam_tags(ctx, int(tags), int(max_cigar_ops), *rest)
-        return self._emit_truth(emit, BAM_SHARE + tag_share(tags), n_reads)
+        `tags` and `fmt` as for emit_sam_device (brx_emit_bam_tags, brx_emit_bam_fmt)."""
+        if not fmt:
+            emit = lambda ctx, *rest: self.lib.brx_emit_bam_tags(ctx, int(tags), int(max_cigar_ops), *rest)
+        else:
+            emit = lambda ctx, *rest: self.lib.brx_emit_bam_fmt(ctx, int(fmt), int(tags), int(max_cigar_ops), *rest)
+        return self._emit_truth(emit, BAM_SHARE + tag_share(tags) + fmt_share(fmt, 'bam'), n_reads)
 
     def bgzf_device(self, data):
         """brx_bgzf_device: a uint8 tensor on this engine's device -> a uint8 tensor (same device) holding BGZF blocks of it, one per

@@ -34,7 +34,7 @@ import time
 import numpy as np
 
 from . import settings
-from .engine import BAM_SHARE, PAF_SHARE, SAM_SHARE, tag_share, RS_BAND, RS_NOFRAG, RS_QMISS, RS_TOO_MANY_SEGS, SimParams
+from .engine import BAM_SHARE, PAF_SHARE, SAM_SHARE, fmt_share, tag_share, RS_BAND, RS_NOFRAG, RS_QMISS, RS_TOO_MANY_SEGS, SimParams
 from .error_model import ErrorModel
 from .fragment_lengths import FragmentLengths
 from .identities import Identities
@@ -360,14 +360,16 @@ def kept_bytes(stats, first, base, last, n_mine):
     return keep, (int(stats['rec_off'][keep - 1] + stats['rec_len'][keep - 1]) if keep else 0)
 
 
-def expected_out_bytes(engine, n_reads, mean_length, truth_paf, truth_sam=False, truth_bam=False, truth_tags=0):
+def expected_out_bytes(engine, n_reads, mean_length, truth_paf, truth_sam=False, truth_bam=False, truth_tags=0, truth_fmt=0):
     """Bytes a batch of `n_reads` reads is expected to leave on the device (with --truth-paf its PAF text, with --truth-sam its SAM records,
-    with --truth-bam its BAM records before they are compressed too, with --truth-tags what the tags add to either): by the engine's estimate
+    with --truth-bam its BAM records before they are compressed too, with --truth-tags what the tags add to either, with --truth-cs /
+    --truth-eqx what they add to each of the three): by the engine's estimate
     from its parameters, or at 2.1 B per base + 400 per read for an engine without one (None: its parameters are not set yet)."""
     per_read = engine.expected_record_bytes() if hasattr(engine, 'expected_record_bytes') else 2.1 * mean_length + 400.0
     out_bytes = int(n_reads * per_read)
     share = (PAF_SHARE if truth_paf else 0.0) + (SAM_SHARE if truth_sam else 0.0) + (BAM_SHARE if truth_bam else 0.0)
     share += tag_share(truth_tags) * (bool(truth_sam) + bool(truth_bam))
+    share += sum(fmt_share(truth_fmt, kind) for kind, on in (('paf', truth_paf), ('sam', truth_sam), ('bam', truth_bam)) if on)
     return int(out_bytes * (1.0 + share)) if share else out_bytes
 
 
@@ -518,7 +520,7 @@ class _ArenaPrefetch(object):
             pass
 
     @staticmethod
-    def for_job(engine, target_size, mean_length, error_rate, in_flight, world, truth_paf=False, truth_sam=False, truth_bam=False, truth_tags=0):
+    def for_job(engine, target_size, mean_length, error_rate, in_flight, world, truth_paf=False, truth_sam=False, truth_bam=False, truth_tags=0, truth_fmt=0):
         """Arenas for the batches in flight of THIS job on THIS device, or None (not a GPU engine, a job of one small batch,
         BRX_ARENA_PREFETCH=0).  How many: what the job will use and the free memory holds (engines_for_memory, no arena mapped yet)."""
         # Measured (profiles/r05i_arena_prefetch.json, r05k_*; DESIGN.md has the figures): the read loop then runs undisturbed, 18.8-19.0 s for
@@ -531,7 +533,7 @@ class _ArenaPrefetch(object):
         if first_batch < 4096:
             return None                                  # a small job: one arena, sized by presize
         nbytes = engine.arena_bytes(first_batch, mean_length, error_rate) if hasattr(engine, 'arena_bytes') else arena_estimate(first_batch, mean_length, error_rate)
-        out_bytes = expected_out_bytes(None, first_batch, mean_length, truth_paf, truth_sam, truth_bam, truth_tags)        # the engine's parameters are not set yet
+        out_bytes = expected_out_bytes(None, first_batch, mean_length, truth_paf, truth_sam, truth_bam, truth_tags, truth_fmt)        # the engine's parameters are not set yet
         batches = -(-int(target_size) // max(int(first_batch * mean_length * max(world, 1)), 1))
         free, _ = engine.torch.cuda.mem_get_info(engine.device)
         n = engines_for_memory(free, max(1, min(int(in_flight), batches)), nbytes, 0, out_bytes, driver_reserve_bytes())
@@ -554,7 +556,7 @@ class _BatchPool(object):
     bytes device-to-device out of the engine's buffer when the batch is done (2 GB at HBM speed: ~1 ms) and gives the engine back at once; `depth` =
     in_flight + 2 batches may be outstanding, the surplus holding only their bytes."""
 
-    def __init__(self, engine, in_flight, arenas=None, device_gzip=False, truth_paf=False, truth_sam=False, truth_bam=False, truth_tags=0):
+    def __init__(self, engine, in_flight, arenas=None, device_gzip=False, truth_paf=False, truth_sam=False, truth_bam=False, truth_tags=0, truth_fmt=0):
         self.arenas = arenas
         self.truth_paf = bool(truth_paf)                 # --truth-paf: every batch's truth alignments, made by its worker beside its FASTQ
         self.truth_sam = bool(truth_sam)                 # --truth-sam: the same as SAM records
@@ -562,6 +564,7 @@ class _BatchPool(object):
         # whole into BGZF blocks on its engine's stream; any other batch's are compressed by the consumer, for the reads it keeps
         self.truth_bam = bool(truth_bam)
         self.truth_tags = int(truth_tags)                # --truth-tags: TAG_MD | TAG_SA on the SAM and BAM records
+        self.truth_fmt = int(truth_fmt)                  # --truth-eqx / --truth-cs: FMT_EQX | FMT_CS | FMT_CS_LONG on the PAF, SAM and BAM records
         # --gzip-device: the worker of a batch that the stop rule cannot cut (submit(..., pack=True)) packs ITS batch on ITS engine's stream and hands
         # over the gzip members; the consumer packs only the job's last batches (every batch there: 10.4 s of configs[4]'s read loop against 6.0 s)
         self.device_gzip = bool(device_gzip)
@@ -651,17 +654,17 @@ class _BatchPool(object):
                 return torch.zeros(0, dtype=torch.uint8), np.zeros(0, dtype=eng.stats_dtype), None, None, None, None
             if not self.on_gpu:
                 out, stats = eng.simulate_batch(seed, first, n_mine, allow_nofrag=True)
-                paf = eng.emit_paf_device(n_mine) if self.truth_paf else None
-                sam = self._sam_of(eng, n_mine, self.truth_tags) if self.truth_sam else None
-                bam = self._bam_of(eng, n_mine, pack, self.truth_tags) if self.truth_bam else None
+                paf = self._paf_of(eng, n_mine, self.truth_fmt) if self.truth_paf else None
+                sam = self._sam_of(eng, n_mine, self.truth_tags, self.truth_fmt) if self.truth_sam else None
+                bam = self._bam_of(eng, n_mine, pack, self.truth_tags, self.truth_fmt) if self.truth_bam else None
                 return torch.from_numpy(np.ascontiguousarray(out).copy()), stats.copy(), None, paf, sam, bam
             torch.cuda.set_device(eng.device)
             with torch.cuda.stream(stream):
                 out, stats = eng.simulate_batch_device(seed, first, n_mine, allow_nofrag=True)
                 # the truth alignments read what the batch left in the engine's arena: same job, same stream, before the engine is free
-                paf = eng.emit_paf_device(n_mine) if self.truth_paf else None
-                sam = self._sam_of(eng, n_mine, self.truth_tags) if self.truth_sam else None
-                bam = self._bam_of(eng, n_mine, pack, self.truth_tags) if self.truth_bam else None
+                paf = self._paf_of(eng, n_mine, self.truth_fmt) if self.truth_paf else None
+                sam = self._sam_of(eng, n_mine, self.truth_tags, self.truth_fmt) if self.truth_sam else None
+                bam = self._bam_of(eng, n_mine, pack, self.truth_tags, self.truth_fmt) if self.truth_bam else None
                 stats = stats.copy()
                 packed = None
                 if pack and self.device_gzip and len(stats) and hasattr(eng, 'gzip_device'):
@@ -681,14 +684,23 @@ class _BatchPool(object):
             self.free.put(i)
 
     @staticmethod
-    def _sam_of(eng, n_mine, tags=0):
-        """The batch's SAM records and read offsets (an engine is asked for tags only when there are some)."""
-        return eng.emit_sam_device(n_mine, tags=tags) if tags else eng.emit_sam_device(n_mine)
+    def _paf_of(eng, n_mine, fmt=0):
+        """The batch's PAF records and read offsets (an engine is asked for formats only when there are some)."""
+        return eng.emit_paf_device(n_mine, fmt=fmt) if fmt else eng.emit_paf_device(n_mine)
 
     @staticmethod
-    def _bam_of(eng, n_mine, pack, tags=0):
+    def _sam_of(eng, n_mine, tags=0, fmt=0):
+        """The batch's SAM records and read offsets (an engine is asked for tags and formats only when there are some)."""
+        kw = dict(tags=tags) if tags else {}
+        if fmt: kw['fmt'] = fmt
+        return eng.emit_sam_device(n_mine, **kw)
+
+    @staticmethod
+    def _bam_of(eng, n_mine, pack, tags=0, fmt=0):
         """The batch's BAM records and read offsets; with `pack` the records' BGZF blocks instead, made at once on the same stream."""
-        data, off = eng.emit_bam_device(n_mine, tags=tags) if tags else eng.emit_bam_device(n_mine)
+        kw = dict(tags=tags) if tags else {}
+        if fmt: kw['fmt'] = fmt
+        data, off = eng.emit_bam_device(n_mine, **kw)
         if pack and int(data.numel()):
             return eng.bgzf_device(data), off, True
         return data, off, False
@@ -705,7 +717,7 @@ class _BatchPool(object):
 
 def run_batches(engine, seed, target_size, mean_length, write, output, shard=None, max_batch=None, in_flight=1, device_gzip=False,
                 local_write=None, local_parts=None, expected_error=None, arenas=None, truth_paf=False, paf_write=None,
-                truth_sam=False, sam_write=None, truth_bam=False, bam_write=None, truth_tags=0):
+                truth_sam=False, sam_write=None, truth_bam=False, bam_write=None, truth_tags=0, truth_fmt=0):
     """
     The `while total_size < target_size` loop (simulate.py:63-86) over super-batches of read indices.
     `write(bytes_like)` receives the FASTQ bytes in read order on rank 0 only.  Returns (read count, total bases).
@@ -740,11 +752,13 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
 
     truth_tags (--truth-tags): TAG_MD | TAG_SA, the tags the SAM and the BAM records carry beside NM and AS.
 
+    truth_fmt (--truth-eqx, --truth-cs): FMT_EQX | FMT_CS | FMT_CS_LONG, =/X CIGAR runs and cs:Z: on the PAF, SAM and BAM records.
+
     A sink that fails on one rank of a multi-rank run (a full disk, a closed pipe) is reported in the same exchange -- one
     word per rank -- so that every rank leaves the loop at the same batch instead of waiting in a collective.
     """
     run = _Run(engine, seed, target_size, mean_length, write, output, shard or Shard(), max_batch or DEFAULT_MAX_BATCH, in_flight,
-               device_gzip, local_write, local_parts, expected_error, arenas, truth_paf, paf_write, truth_sam, sam_write, truth_bam, bam_write, truth_tags)
+               device_gzip, local_write, local_parts, expected_error, arenas, truth_paf, paf_write, truth_sam, sam_write, truth_bam, bam_write, truth_tags, truth_fmt)
     run_batches.last_timing = run.timing
     run.size_pipeline()
     run.open_rings()
@@ -767,14 +781,14 @@ class _Run(object):
 
     def __init__(self, engine, seed, target_size, mean_length, write, output, shard, max_batch, in_flight, device_gzip,
                  local_write, local_parts, expected_error, arenas, truth_paf, paf_write, truth_sam=False, sam_write=None,
-                 truth_bam=False, bam_write=None, truth_tags=0):
+                 truth_bam=False, bam_write=None, truth_tags=0, truth_fmt=0):
         import torch
         self.torch = torch
         self.engine, self.seed, self.target_size, self.write, self.output, self.shard = engine, seed, target_size, write, output, shard
         self.max_batch, self.in_flight, self.device_gzip, self.expected_error, self.arenas = max_batch, in_flight, device_gzip, expected_error, arenas
         self.local_write, self.local_parts, self.truth_paf, self.paf_write = local_write, local_parts, truth_paf, paf_write
         self.truth_sam, self.sam_write = truth_sam, sam_write
-        self.truth_bam, self.bam_write, self.truth_tags = truth_bam, bam_write, int(truth_tags)
+        self.truth_bam, self.bam_write, self.truth_tags, self.truth_fmt = truth_bam, bam_write, int(truth_tags), int(truth_fmt)
         self.count = self.total = self.next_read = 0
         self.expected_mean = float(mean_length)
         self.pending = collections.deque()          # _Pending, in index order
@@ -796,7 +810,8 @@ class _Run(object):
                 engine.adopt_scratch(first_arena)
             else:                                    # by the job's identity law, if given: arenas for Q30 reads are half those of 95 % reads
                 engine.presize(first_batch, self.expected_mean, self.expected_error)
-            out_bytes = expected_out_bytes(engine, first_batch, self.expected_mean, self.truth_paf, self.truth_sam, self.truth_bam, self.truth_tags)
+            out_bytes = expected_out_bytes(engine, first_batch, self.expected_mean, self.truth_paf, self.truth_sam, self.truth_bam, self.truth_tags,
+                                           self.truth_fmt)
         asked = fit = max(1, int(self.in_flight))
         if first_arena is not None:
             fit = min(fit, arenas.count)             # decided when the arenas were requested, by the same rule, from the memory that was free then
@@ -807,7 +822,7 @@ class _Run(object):
         if fit < asked and shard.rank == 0:
             print(f'  {fit} of the {asked} batches in flight asked for fit into the free device memory', file=self.output)
         self.pool = _BatchPool(engine, fit, arenas, device_gzip=self.device_gzip, truth_paf=self.truth_paf, truth_sam=self.truth_sam,
-                               truth_bam=self.truth_bam, truth_tags=self.truth_tags)
+                               truth_bam=self.truth_bam, truth_tags=self.truth_tags, truth_fmt=self.truth_fmt)
         self.timing['create_engines'] = time.perf_counter() - self.t_job
 
     def open_rings(self):
@@ -1209,11 +1224,12 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
     engine.set_reference(pref, cum_weight)
     mark('reference_on_device')
     truth_tags = int(getattr(args, 'truth_tags', None) or 0)                     # --truth-tags: TAG_MD | TAG_SA (check_simulate_args)
+    truth_fmt = int(getattr(args, 'truth_fmt', None) or 0)                       # --truth-eqx, --truth-cs: FMT_EQX | FMT_CS | FMT_CS_LONG
     # the job's arenas from now on, beside everything below (models, tables, the first batch): _ArenaPrefetch
     arenas = _ArenaPrefetch.for_job(engine, get_target_size(pref.n_bases, args.quantity), float(args.mean_frag_length),
                                     expected_error_rate(identities), getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, shard.world,
                                     truth_paf=bool(getattr(args, 'truth_paf', None)), truth_sam=bool(getattr(args, 'truth_sam', None)),
-                                    truth_bam=bool(getattr(args, 'truth_bam', None)), truth_tags=truth_tags)
+                                    truth_bam=bool(getattr(args, 'truth_bam', None)), truth_tags=truth_tags, truth_fmt=truth_fmt)
     # a model file that is not in the cache is aligned (align_kmers, error_model.py:179-229) on THIS engine
     error_model = ErrorModel(args.error_model, quiet, aligner=lambda qs, ts: engine.align_batch(qs, ts)[0])
     qscore_model = QScoreModel(args.qscore_model, quiet)
@@ -1241,7 +1257,8 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
                                  local_write=outs.local_write, local_parts=outs.local_parts, expected_error=expected_error_rate(identities),
                                  arenas=arenas, truth_paf=bool(getattr(args, 'truth_paf', None)), paf_write=outs.paf_write,
                                  truth_sam=bool(getattr(args, 'truth_sam', None)), sam_write=outs.sam_write,
-                                 truth_bam=bool(getattr(args, 'truth_bam', None)), bam_write=outs.bam_write, truth_tags=truth_tags)
+                                 truth_bam=bool(getattr(args, 'truth_bam', None)), bam_write=outs.bam_write, truth_tags=truth_tags,
+                                 truth_fmt=truth_fmt)
         finally:
             outs.close()
     except (SystemExit, OSError):

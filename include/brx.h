@@ -395,6 +395,24 @@ int brx_emit_sam_tags(brx_ctx *ctx, uint32_t tags, uint8_t *d_out, size_t out_ca
 int brx_emit_bam_tags(brx_ctx *ctx, uint32_t tags, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off,
                       size_t *out_bytes, void *hip_stream);
 
+/* brx_emit_paf / brx_emit_sam_tags / brx_emit_bam_tags with minimap2's --eqx and --cs on every truth file (fmt: BRX_FMT_* bits; 0 =
+ * exactly the functions above; an unknown bit, or BRX_FMT_CS_LONG without BRX_FMT_CS: BRX_E_ARG), under the same contract: BRX_E_STATE,
+ * BRX_E_OUTPUT + brx_output_needed() with nothing written, stateless, callable in any order with the other emitters.  Records, their
+ * order, the primaries and every field not named here are those of fmt 0.
+ *   BRX_FMT_EQX      CIGAR runs are maximal runs of one op, = X I D (BAM: 7 8 1 2), in cg:Z:, the SAM CIGAR and the BAM operations; the
+ *                    clips stay S / H.  n_cigar_op, and so max_cigar_ops and CG:B:I, count these runs.  SA:Z: keeps its compact CIGAR.
+ *   BRX_FMT_CS       cs:Z: on every PAF record (last field) and every mapped SAM / BAM line (NM AS [MD] [cs] [SA] [CO], CG last): the
+ *                    record's columns in reference-forward order (from its last column on '-'), a run of n '=' as `:n`, an X as `*rq`, a
+ *                    run of I as `+q..`, a run of D as `-r..`; r = the fragment's base that MD:Z: writes, q = the read's base that SEQ
+ *                    writes (both through brx_reference.sym, on '-' complemented through brx_reference.comp), in lower case (c | 0x20).
+ *   BRX_FMT_CS_LONG  a run of '=' as `=` and its r bases as they are, instead of `:n` (README: --truth-cs, --truth-eqx). */
+enum { BRX_FMT_EQX = 1u, BRX_FMT_CS = 2u, BRX_FMT_CS_LONG = 4u };
+int brx_emit_paf_fmt(brx_ctx *ctx, uint32_t fmt, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream);
+int brx_emit_sam_fmt(brx_ctx *ctx, uint32_t fmt, uint32_t tags, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes,
+                     void *hip_stream);
+int brx_emit_bam_fmt(brx_ctx *ctx, uint32_t fmt, uint32_t tags, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off,
+                     size_t *out_bytes, void *hip_stream);
+
 /* n_bytes of device memory as BGZF blocks (SAM spec v1 section 4.1) back to back, one per BRX_BGZF_BLOCK input bytes, the last
  * one possibly shorter, none for no input: the members of brx_gzip_device (one dynamic Huffman code per block, no match search)
  * behind the 18-byte BGZF header (FEXTRA, 'B' 'C', BSIZE = the block's size - 1).  A block needs at most 61 607 bytes, so every
