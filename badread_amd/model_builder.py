@@ -13,6 +13,7 @@ window recorded per key.
 """
 import collections
 import itertools
+import re
 import sys
 
 import numpy as np
@@ -88,10 +89,12 @@ class Job(object):
         return ''.join(read), ''.join(qual), ''.join(ref)
 
 
-def _table(engine, kind, job, k, max_del, n_ksizes):
-    bits = 16
+def _table(engine, kind, job, k, max_del, n_ksizes, first_bits=16):
+    """The counted table of a job.  The first table has 2^first_bits slots, raised to four times the keys the job is expected to hold;
+    a first_bits below the default is taken as it is, so the growth below is what finds the size."""
+    bits = first_bits
     need = max(job.n_cols * (n_ksizes if kind else 1) // 2, 1)
-    while (1 << bits) < 4 * need and bits < 28:
+    while first_bits >= 16 and (1 << bits) < 4 * need and bits < 28:
         bits += 1
     while True:
         res = engine.model_count(kind, job, k, max_del, n_ksizes, bits)
@@ -100,6 +103,39 @@ def _table(engine, kind, job, k, max_del, n_ksizes):
         bits += 2                                   # table full: the engine returned None
         if bits > 30:
             sys.exit('Error: model builder hash table does not fit')
+
+
+def _spilled(spill, shift, strings_of):
+    """(word, strings_of(its alignment)) for every distinct spilled word, ascending; the alignment index is the word's top bits, so
+    the words of one alignment follow each other and its strings are built once, not once per word."""
+    held, strings = -1, None
+    for word in sorted(set(spill.tolist())):
+        if word >> shift != held:
+            held = word >> shift
+            strings = strings_of(held)
+        yield word, strings
+
+
+def count_error_model(engine, job, k, first_bits=16):
+    """(ref k-mer, read k-mer) -> [count, earliest window (alignment << 32 | start column)]: the device table with the spilled
+    windows merged in."""
+    keys, counts, first, spill = _table(engine, 0, job, k, 0, 1, first_bits)
+    found = {}
+    mask_k = (1 << (2 * k)) - 1
+    for key, n, rank in zip(keys.tolist(), counts.tolist(), first.tolist()):
+        refk = key & mask_k
+        length = (key >> (2 * k)) & 31
+        bits = key >> (2 * k + 5)
+        ref_kmer = ''.join('ACGT'[(refk >> (2 * (k - 1 - i))) & 3] for i in range(k))
+        read_kmer = ''.join('ACGT'[(bits >> (2 * i)) & 3] for i in range(length))
+        found[(ref_kmer, read_kmer)] = [n, rank]
+    for word, (read_g, _, ref_g) in _spilled(spill, 32, lambda a: job.gapped(a, '-')):       # read k-mers of more than 21 bases: counted here
+        pair = _error_window(read_g, ref_g, word & 0xFFFFFFFF, k)
+        if pair is not None:
+            entry = found.setdefault(pair, [0, word])
+            entry[0] += 1
+            entry[1] = min(entry[1], word)
+    return found
 
 
 def make_error_model(args, output=sys.stderr, dot_interval=1000, engine=None, stdout=None):
@@ -116,27 +152,8 @@ def make_error_model(args, output=sys.stderr, dot_interval=1000, engine=None, st
         from .engine import default_engine
         engine = default_engine()
     print('Processing alignments', end='', file=output, flush=True)
-    job = Job(refs, reads, alignments)
-    keys, counts, first, spill = _table(engine, 0, job, k, 0, 1)
+    found = count_error_model(engine, Job(refs, reads, alignments), k)
     print('.' * (len(alignments) // dot_interval), file=output, flush=True)
-    # (ref k-mer, read k-mer) -> [count, earliest window]
-    found = {}
-    mask_k = (1 << (2 * k)) - 1
-    for key, n, rank in zip(keys.tolist(), counts.tolist(), first.tolist()):
-        refk = key & mask_k
-        length = (key >> (2 * k)) & 31
-        bits = key >> (2 * k + 5)
-        ref_kmer = ''.join('ACGT'[(refk >> (2 * (k - 1 - i))) & 3] for i in range(k))
-        read_kmer = ''.join('ACGT'[(bits >> (2 * i)) & 3] for i in range(length))
-        found[(ref_kmer, read_kmer)] = [n, rank]
-    for word in sorted(set(spill.tolist())):        # read k-mers of more than 21 bases: counted here
-        a, start = word >> 32, word & 0xFFFFFFFF
-        read_g, _, ref_g = job.gapped(a, '-')
-        pair = _error_window(read_g, ref_g, start, k)
-        if pair is not None:
-            entry = found.setdefault(pair, [0, word])
-            entry[0] += 1
-            entry[1] = min(entry[1], word)
     by_kmer = collections.defaultdict(list)
     for (ref_kmer, read_kmer), (n, rank) in found.items():
         by_kmer[ref_kmer].append((rank, read_kmer, n))
@@ -167,6 +184,42 @@ def _error_window(read_g, ref_g, start, k):
     return None
 
 
+def count_qscore_model(engine, job, k_size, max_del, first_bits=16):
+    """cigar -> [earliest window (alignment << 40 | size index << 36 | start column), {q: count}]: the device table with the
+    spilled windows merged in."""
+    keys, counts, first, spill = _table(engine, 1, job, k_size, max_del, (k_size + 1) // 2, first_bits)
+    per_cigar = {}
+    for key, n, rank in zip(keys.tolist(), counts.tolist(), first.tolist()):
+        q, ki, ops = key & 127, (key >> 7) & 15, key >> 11
+        cigar, shift = [], 0
+        for i in range(2 * ki + 1):
+            if i:
+                cigar.append('D' * ((ops >> shift) & 15)); shift += 4
+            cigar.append('=XI'[(ops >> shift) & 3]); shift += 2
+        entry = per_cigar.setdefault(''.join(cigar), [rank, collections.Counter()])
+        entry[0] = min(entry[0], rank)
+        entry[1][q] += n
+    # windows a key cannot hold (k_mb_qscore names each: alignment, size index, start)
+    long_run = re.compile('D{' + str(max_del) + ',}')
+
+    def strings_of(a):                               # gapped read and quality, and the alignment's columns as cigar letters
+        read_g, qual_g, ref_g = job.gapped(a, ' ')
+        return read_g, qual_g, ''.join('=' if r == f else 'D' if r == ' ' else 'I' if f == ' ' else 'X' for r, f in zip(read_g, ref_g))
+
+    for word, (read_g, qual_g, ops_g) in _spilled(spill, 36, strings_of):
+        a, ki, start = word >> 36, (word >> 32) & 15, word & 0xFFFFFFFF
+        hit = _qscore_window(read_g, qual_g, ops_g, start, 2 * ki + 1, long_run, 'D' * max_del)
+        if hit is None:
+            continue
+        rank = (a << 40) | (ki << 36) | start
+        entry = per_cigar.get(hit[0])
+        if entry is None:
+            entry = per_cigar[hit[0]] = [rank, collections.Counter()]
+        entry[0] = min(entry[0], rank)
+        entry[1][hit[1]] += 1
+    return per_cigar
+
+
 def make_qscore_model(args, output=sys.stderr, dot_interval=1000, engine=None, stdout=None):
     stdout = stdout or sys.stdout
     refs, _, _, _, _ = load_fasta(args.reference)
@@ -182,30 +235,8 @@ def make_qscore_model(args, output=sys.stderr, dot_interval=1000, engine=None, s
         from .engine import default_engine
         engine = default_engine()
     print('Processing alignments', end='', file=output, flush=True)
-    job = Job(refs, reads, alignments)
-    keys, counts, first, spill = _table(engine, 1, job, args.k_size, args.max_del, n_ksizes)
+    per_cigar = count_qscore_model(engine, Job(refs, reads, alignments), args.k_size, args.max_del)
     print('.' * (len(alignments) // dot_interval), file=output, flush=True)
-    per_cigar = {}                                   # cigar -> [earliest window, {q: count}]
-    for key, n, rank in zip(keys.tolist(), counts.tolist(), first.tolist()):
-        q, ki, ops = key & 127, (key >> 7) & 15, key >> 11
-        cigar, shift = [], 0
-        for i in range(2 * ki + 1):
-            if i:
-                cigar.append('D' * ((ops >> shift) & 15)); shift += 4
-            cigar.append('=XI'[(ops >> shift) & 3]); shift += 2
-        entry = per_cigar.setdefault(''.join(cigar), [rank, collections.Counter()])
-        entry[0] = min(entry[0], rank)
-        entry[1][q] += n
-    for word in sorted(set(spill.tolist())):         # windows a key cannot hold (k_mb_qscore names each: alignment, size index, start)
-        a, ki, start = word >> 36, (word >> 32) & 15, word & 0xFFFFFFFF
-        read_g, qual_g, ref_g = job.gapped(a, ' ')
-        hit = _qscore_window(read_g, qual_g, ref_g, start, 2 * ki + 1, args.max_del)
-        if hit is None:
-            continue
-        rank = (a << 40) | (ki << 36) | start
-        entry = per_cigar.setdefault(hit[0], [rank, collections.Counter()])
-        entry[0] = min(entry[0], rank)
-        entry[1][hit[1]] += 1
     overall = collections.Counter()
     for cigar, (_, qs) in per_cigar.items():
         if len(cigar.replace('D', '')) == 1:         # every window of one read base (qscore_model.py:141-142)
@@ -219,19 +250,19 @@ def make_qscore_model(args, output=sys.stderr, dot_interval=1000, engine=None, s
             break
 
 
-def _qscore_window(read_g, qual_g, ref_g, start, k_size, max_del):
-    """One window of qscore_model.py:104-143 on the gapped strings: (cigar, qscore) or None."""
-    import re
-    end = start
-    while len(read_g[start:end].replace(' ', '')) < k_size:
-        end += 1
-        if end > len(read_g):
+def _qscore_window(read_g, qual_g, ops_g, start, k_size, long_run, run_cap):
+    """One window of qscore_model.py:104-143 on the gapped strings (ops_g: the columns as = X I D): (cigar, qscore) or None."""
+    end = start + k_size
+    if end > len(read_g):
+        return None
+    have = k_size - read_g.count(' ', start, end)
+    while have < k_size:
+        if end >= len(read_g):
             return None
-    cigar = ''.join('=' if r == f else 'D' if r == ' ' else 'I' if f == ' ' else 'X'
-                    for r, f in zip(read_g[start:end], ref_g[start:end]))
-    cigar = re.sub('D{' + str(max_del) + ',}', 'D' * max_del, cigar)
+        have += read_g[end] != ' '
+        end += 1
     qual = qual_g[start:end].replace(' ', '')
-    return cigar, ord(qual[(k_size - 1) // 2]) - 33
+    return long_run.sub(run_cap, ops_g[start:end]), ord(qual[(k_size - 1) // 2]) - 33
 
 
 def print_qscore_fractions(cigar, qscores, min_occur, stdout):

@@ -1,7 +1,8 @@
 """
 GPU: --truth-paf on the MI355X.  The emulated-device checks of tests/test_truth_paf.py on the HIP engine (exact PAF at 100 %
 identity, properties of errorful records), the command line (PAF independent of streams, batch sizes and ranks; FASTQ
-unchanged by the flag) and the round trip through the model builders.
+unchanged by the flag), the round trip through the model builders, and the builders' text on a 60x truth PAF against the plain
+restatement of the reference's counting loops.
 """
 import collections
 import io
@@ -110,6 +111,33 @@ def test_truth_paf_builds_models(tmp_path):
     # tolerance set from one run on the MI355X: max |difference| 0.219 (a 3.6 kb reference sees each of these 7-mers only a
     # few hundred times over the job, so the built probabilities are noisy); 0.3 leaves room for that noise, not for a bias
     assert diff < 0.3, diff
+
+
+def test_truth_paf_models_equal_the_restatement_at_scale(tmp_path):
+    """The builder commands on a truth PAF of 60x: thousands of windows per key, '-' strands, and reads with several records of which
+    the loader keeps one.  Their stdout (the commands' default arguments) equals the text the plain restatement
+    (oracle/model_builder_ref.py) gives for the same files, read through the product's loaders."""
+    sys.path.insert(0, os.path.join(REPO, 'oracle'))
+    import model_builder_ref as R
+    from badread_amd.alignment import load_alignments
+    from badread_amd.misc import load_fasta, load_fastq, reverse_complement
+    fq, paf = run_cli(tmp_path, 'sc.paf', quantity='60x', length='1000,500')
+    (tmp_path / 'sc.fastq').write_bytes(fq)
+    files = dict(reference=SMALL_REF, reads=str(tmp_path / 'sc.fastq'), alignment=str(tmp_path / 'sc.paf'))
+    refs = load_fasta(files['reference'])[0]
+    reads = load_fastq(files['reads'], output=io.StringIO())
+    al = load_alignments(files['alignment'], None, output=io.StringIO())
+    records = collections.Counter(line.split(b'\t')[0] for line in paf.splitlines())
+    assert len(al) > 100 and {a.strand for a in al} == {'+', '-'} and max(records.values()) > 1 and len(al) < sum(records.values())
+    want = {'error_model': R.error_model_text(refs, reads, al, 7, 25, reverse_complement),
+            'qscore_model': R.qscore_model_text(refs, reads, al, 9, 6, 100, 10000, reverse_complement)}
+    args = [x for key, value in files.items() for x in ('--' + key, value)]
+    for kind in ('error_model', 'qscore_model'):
+        r = subprocess.run([sys.executable, '-m', 'badread_amd', kind] + args, cwd=REPO, capture_output=True, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        got = r.stdout.decode()
+        print('truth_paf_scale', kind, dict(alignments=len(al), lines=got.count('\n'), first_diff=next((i for i, (x, y) in enumerate(zip(got, want[kind])) if x != y), -1)))
+        assert got == want[kind], kind
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -36,6 +36,10 @@ Fixtures written (each records reference version + how it was produced):
                        synthetic error- and qscore-model FILES (tests/custom_models.py: nothing in them comes from the
                        reference) and the same replay under them: the reference loads the files itself.
 
+  model_builder_edges/*, model_builder_edges.json.gz
+                       the file form of the `edges` job of tests/model_jobs.py and the text the reference's own
+                       make_error_model / make_qscore_model print for it -- see make_model_builder_edges().
+
 Run:  python tools/make_golden.py        (needs /root/reference; ~1 minute)
 """
 import collections
@@ -54,7 +58,8 @@ for p in (REPO, os.path.join(REPO, 'oracle'), os.path.join(REPO, 'tests'), os.pa
     if p not in sys.path:
         sys.path.insert(0, p)
 
-import badread.error_model as ref_em          # noqa: E402  (the reference)
+import badread.alignment as ref_alignment    # noqa: E402  (the reference)
+import badread.error_model as ref_em          # noqa: E402
 import badread.fragment_lengths as ref_fl     # noqa: E402
 import badread.identities as ref_id           # noqa: E402
 import badread.misc as ref_misc               # noqa: E402
@@ -829,10 +834,44 @@ def make_model_builders():
     dump('model_builder.json.gz', out)
 
 
+MODEL_BUILDER_EDGES_CASES = {
+    'error': [dict(k_size=k, max_alignments=None, max_alt=10 ** 6) for k in (2, 3, 8)],
+    'qscore': [dict(k_size=ks, max_alignments=None, max_del=md, min_occur=1, max_output=10 ** 6) for ks, md in ((1, 1), (11, 1), (15, 15))],
+}
+
+
+def make_model_builder_edges():
+    """The file form of the `edges` job of tests/model_jobs.py (every alignment passes the loader; ASCII qualities) under
+    tests/golden/model_builder_edges/, and the text the REFERENCE's own make_error_model / make_qscore_model print for these files
+    with nothing cut from it (max_alt, max_output 10**6, min_occur 1): k-mer sizes at both ends of the error key, a qscore key that
+    no longer holds its largest windows (k_size 11, 15) and max_del 1 and 15."""
+    import contextlib
+    import types
+    import model_jobs
+    folder = os.path.join(GOLDEN, 'model_builder_edges')
+    made = model_jobs.edges(files=True)
+    model_jobs.write_files(folder, made)
+    files = dict(reference=os.path.join(folder, 'ref.fasta'), reads=os.path.join(folder, 'reads.fastq'), alignment=os.path.join(folder, 'aln.paf'))
+    kept = ref_alignment.load_alignments(files['alignment'], None, output=io.StringIO())
+    assert len(kept) == len(made[2]), (len(kept), len(made[2]))          # nothing the generator made is dropped by the loader
+    out = {'error': [], 'qscore': []}
+    for kind, fn in (('error', ref_em.make_error_model), ('qscore', ref_qm.make_qscore_model)):
+        for case in MODEL_BUILDER_EDGES_CASES[kind]:
+            buf = io.StringIO()
+            with contextlib.redirect_stdout(buf):
+                fn(types.SimpleNamespace(**files, **case), output=io.StringIO())
+            out[kind].append({'args': case, 'text': buf.getvalue()})
+            print(f'  model builder edges {kind} {case}: {len(buf.getvalue())} characters, {buf.getvalue().count(chr(10))} lines')
+    dump('model_builder_edges.json.gz', out)
+
+
 if __name__ == '__main__':
     os.makedirs(GOLDEN, exist_ok=True)
     if len(sys.argv) > 1 and sys.argv[1] == 'model_builders':
         make_model_builders()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'model_builder_edges':
+        make_model_builder_edges()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'random_change':
         make_random_change()
@@ -860,6 +899,7 @@ if __name__ == '__main__':
     make_random_change()
     make_qscore_top_rows()
     make_model_builders()
+    make_model_builder_edges()
     make_sequence_fragment_bound()
     make_sequence_fragment_lowcomplexity()
     make_sequence_fragment_custom_models()
