@@ -96,45 +96,32 @@ __device__ void bam_bases(const BamNib &T, const SamRead &M, uint8_t *seq, uint8
    byte by byte.  The runs are paf_cigar's. */
 template <bool EQX>
 __device__ void bam_cigar(const PafRead &R, const PafRec &q, uint8_t *ops, uint32_t runs, bool minus) {
-    const int lane = lane_id();
-    const uint64_t below = (1ull << lane) - 1ull;
+    const uint64_t below = (1ull << lane_id()) - 1ull;
     uint32_t done = 0, run_start = q.c0;
     for (uint32_t b = q.c0; b <= q.c1; b += 64) {
-        const uint32_t c = b + lane;
-        const bool in = c <= q.c1;
-        const uint32_t op = in ? R.ops[c] : 0u;
-        const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
-        const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
-        const bool rs = in && (c == q.c0 || paf_run<EQX>(prev) != paf_run<EQX>(op));
-        const bool re = in && (c == q.c1 || paf_run<EQX>(next) != paf_run<EQX>(op));
-        const uint64_t rmask = __ballot(rs), emask = __ballot(re);
-        const uint64_t mine = rmask & (below | (1ull << lane));
-        const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
-        if (re) {
-            const uint32_t i = done + (uint32_t)__popcll(emask & below);
+        const RunStep s = run_step<EQX>(R, q, b, run_start);
+        const uint64_t emask = __ballot(s.re);
+        if (s.re) {
+            const uint32_t i = done + (uint32_t)__popcll(emask & below), op = s.op;
             const uint32_t code = op == 2 ? (uint32_t)BAM_OP_I : op == 3 ? (uint32_t)BAM_OP_D : !EQX ? (uint32_t)BAM_OP_M : op == 0 ? (uint32_t)BAM_OP_EQ : (uint32_t)BAM_OP_X;
-            const uint32_t word = ((c - s0 + 1u) << 4) | code;
+            const uint32_t word = ((s.c - s.s0 + 1u) << 4) | code;
             uint8_t *p = ops + 4ull * (minus ? runs - 1u - i : i);
             p[0] = (uint8_t)word; p[1] = (uint8_t)(word >> 8); p[2] = (uint8_t)(word >> 16); p[3] = (uint8_t)(word >> 24);
         }
         done += (uint32_t)__popcll(emask);
-        if (rmask) run_start = b + (uint32_t)paf_top(rmask);
+        run_start = s.next_start;
     }
 }
 
 template <class S> __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q);
-template <uint32_t TAGS, bool F> struct BamCount {                       /* F: with BRX_FMT_* bits, as brx_sam.h's sinks */
-    static constexpr bool write = false, fmtd = F, need_f0 = (TAGS & BRX_TAG_MD) != 0 || F; static constexpr uint32_t tags = TAGS;
-    uint8_t *out; SamRead M; uint32_t max_ops, surplus, fmt; BamNib T; SaRead A;
+/* brx_sam.h's sink with the longest CIGAR a record may hold in its field (max_ops) and the nibble table of the bases (T: writing only).
+   The writing sink must not grow: the compiler keeps it in LDS, where the 80 bytes per lane it has are all that fit (5120 bytes for a
+   wave at eight waves per SIMD); a word more and it goes to scratch. */
+template <bool WRITE, uint32_t TAGS, bool F> struct BamSink {
+    static constexpr bool write = WRITE, fmtd = F, need_f0 = (TAGS & BRX_TAG_MD) != 0 || F; static constexpr uint32_t tags = TAGS;
+    uint8_t *out; SamRead M; uint32_t max_ops; [[no_unique_address]] SizingWord<WRITE> surplus; uint32_t fmt; BamNib T; SaRead A;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { bam_record(*this, d, R, q); }
 };
-template <uint32_t TAGS, bool F> struct BamWrite {
-    static constexpr bool write = true, fmtd = F, need_f0 = (TAGS & BRX_TAG_MD) != 0 || F; static constexpr uint32_t tags = TAGS;
-    uint8_t *out; SamRead M; uint32_t max_ops, fmt; BamNib T; SaRead A;
-    __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { bam_record(*this, d, R, q); }
-};
-template <uint32_t TAGS, bool F> __device__ __forceinline__ void sink_surplus(BamCount<TAGS, F> &k, uint32_t v) { k.surplus = v; }
-template <uint32_t TAGS, bool F> __device__ __forceinline__ void sink_surplus(BamWrite<TAGS, F> &, uint32_t) {}
 #define BRX_BAM_ZTAG 4u                /* a Z tag around its text: two letters, 'Z' and the NUL */
 
 __device__ __forceinline__ uint32_t bam_bases_bytes(uint32_t l_seq) { return (l_seq + 1u) / 2u + l_seq; }       /* SEQ and QUAL */
@@ -143,37 +130,18 @@ __device__ __forceinline__ uint32_t bam_bases_bytes(uint32_t l_seq) { return (l_
    written.  Every lane calls it (wave-uniform arguments). */
 template <class S>
 __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q) {
-    const uint32_t fmt = sink_fmt(sink);
-    const bool eqx = (fmt & BRX_FMT_EQX) != 0;
-    const PafShape sh = eqx ? paf_shape<true>(R, q) : paf_shape<false>(R, q);     /* with EQX the runs, and so the long form, are the =/X CIGAR's */
-    const uint32_t nm = sh.cnt[1] + sh.cnt[2] + sh.cnt[3];
-    const int64_t as = (int64_t)sh.cnt[0] - (int64_t)nm;
-    const uint32_t qcols = sh.cnt[0] + sh.cnt[1] + sh.cnt[2], tspan = sh.cnt[0] + sh.cnt[1] + sh.cnt[3];
-    const bool minus = ((q.key0 >> 32) & 1u) != 0;
-    const uint32_t L = R.seq_len, qs = q.r0 - R.start_trim, qe = qs + qcols;
-    const uint32_t left = minus ? L - qe : qs, right = minus ? qs : L - qe;
-    const uint32_t line = R.n_rec;
-    const bool primary = S::write && line == R.best;
-    const bool top = paf_rank(R, as);
-    /* MD and SA as Z tags (a sized record counts no SA: k_bam_size adds the read's at the end) */
-    MdShape md; md.text = md.tail = 0;
-    uint32_t md_len = 0, sa_len = 0;
-    if (S::tags & BRX_TAG_MD) { md = md_sweep<false>(d, R, q, minus, nullptr, md); md_len = BRX_BAM_ZTAG + md.text; }
-    if (S::tags & BRX_TAG_SA) {
-        if (!S::write) sink.A.sum += sa_rec_of(d, R, q, sh).len;
-        else if (sink.A.n) sa_len = BRX_BAM_ZTAG + sink.A.sum - sink.A.tab[line].len;
-    }
-    uint32_t cs_text = 0, cs_len = 0;                                                 /* cs as a Z tag between MD and SA */
-    if constexpr (S::fmtd) if (fmt & BRX_FMT_CS) {
-        cs_text = cs_sweep<false>(d, R, q, minus, (fmt & BRX_FMT_CS_LONG) != 0, nullptr, nullptr, 0u);
-        cs_len = BRX_BAM_ZTAG + cs_text;
-    }
-    const uint32_t n_ops = sh.runs + (left ? 1u : 0u) + (right ? 1u : 0u);
+    const RecGeom g = rec_geom(sink, d, R, q);       /* with EQX the runs, and so the long form, are the =/X CIGAR's */
+    const bool primary = g.primary, minus = g.minus;
+    const uint32_t left = g.left, right = g.right, tspan = g.tspan;
+    /* MD, cs and SA as Z tags, in this order */
+    const uint32_t md_len = (S::tags & BRX_TAG_MD) ? BRX_BAM_ZTAG + g.md.text : 0u;
+    const uint32_t cs_len = g.cs ? BRX_BAM_ZTAG + g.cs_text : 0u, sa_len = g.sa ? BRX_BAM_ZTAG + g.sa_text : 0u;
+    const uint32_t n_ops = g.sh.runs + (left ? 1u : 0u) + (right ? 1u : 0u);
     const bool lng = n_ops > sink.max_ops;
     const uint32_t n_cigar = lng ? 2u : n_ops;
     const uint32_t comment = sam_comment(sink);
-    const uint32_t bases = primary ? L : qcols;
-    CountSink tc; tc.n = 0; bam_tags(tc, nm, as);
+    const uint32_t bases = primary ? g.L : g.qcols;
+    CountSink tc; tc.n = 0; bam_tags(tc, g.nm, g.as);
     const uint32_t seq_at = BRX_BAM_CIGAR_AT + 4u * n_cigar, qual_at = seq_at + (bases + 1u) / 2u, tag_at = qual_at + bases;
     const uint32_t cg_at = tag_at + tc.n + md_len + cs_len + sa_len + (primary ? 4u + comment : 0u);     /* CO Z comment NUL */
     const uint32_t bytes = cg_at + (lng ? 8u + 4u * n_ops : 0u);                                 /* CG B I count, the words */
@@ -190,23 +158,22 @@ __device__ void bam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q
             if (left) { ByteSink c; c.p = ops; c.n = 0; put_le(c, (left << 4) | clip, 4); }
             if (right) { ByteSink c; c.p = ops + 4ull * (n_ops - 1u); c.n = 0; put_le(c, (right << 4) | clip, 4); }
             ByteSink t; t.p = o + tag_at; t.n = 0;
-            bam_tags(t, nm, as);
-            if (md_len) { t.put('M'); t.put('D'); t.put('Z'); t.n += md.text; t.put(0); }          /* the texts are the wave's, below */
-            if (cs_len) { t.put('c'); t.put('s'); t.put('Z'); t.n += cs_text; t.put(0); }
-            if (sa_len) { t.put('S'); t.put('A'); t.put('Z'); t.n += sa_len - BRX_BAM_ZTAG; t.put(0); }
+            bam_tags(t, g.nm, g.as);
+            if (md_len) { t.put('M'); t.put('D'); t.put('Z'); t.n += g.md.text; t.put(0); }          /* the texts are the wave's, below */
+            if (cs_len) { t.put('c'); t.put('s'); t.put('Z'); t.n += g.cs_text; t.put(0); }
+            if (sa_len) { t.put('S'); t.put('A'); t.put('Z'); t.n += g.sa_text; t.put(0); }
             if (primary) { t.put('C'); t.put('O'); t.put('Z'); put_comment(t, d, *sink.M.s, sink.M.pieces); t.put(0); }
             if (lng) { t.put('C'); t.put('G'); t.put('B'); t.put('I'); put_le(t, n_ops, 4); }
         }
-        if (md_len) md_sweep<true>(d, R, q, minus, o + tag_at + tc.n + 3u, md);
+        if (md_len) md_sweep<true>(d, R, q, minus, o + tag_at + tc.n + 3u, g.md);
         if constexpr (S::fmtd) if (cs_len)
-            cs_sweep<true>(d, R, q, minus, (fmt & BRX_FMT_CS_LONG) != 0, sink.M.seq, o + tag_at + tc.n + md_len + 3u, cs_text);
-        if (sa_len) sa_write(d, sink.A, line, R.best, o + tag_at + tc.n + md_len + cs_len + 3u);
-        if (eqx) bam_cigar<true>(R, q, ops + (left ? 4u : 0u), sh.runs, minus); else bam_cigar<false>(R, q, ops + (left ? 4u : 0u), sh.runs, minus);
-        bam_bases(sink.T, sink.M, o + seq_at, o + qual_at, primary ? 0u : qs, primary ? L : qe, minus);
-    } else if (top) {
-        /* the same record as the primary: SEQ and QUAL are the whole read, CO:Z:; the operations stay as many (S for H) */
-        sink_surplus(sink, bam_bases_bytes(L) - bam_bases_bytes(qcols) + 4u + comment);
+            cs_sweep<true>(d, R, q, minus, g.cs_long, sink.M.seq, o + tag_at + tc.n + md_len + 3u, g.cs_text);
+        if (sa_len) sa_write(d, sink.A, g.line, R.best, o + tag_at + tc.n + md_len + cs_len + 3u);
+        if (g.eqx) bam_cigar<true>(R, q, ops + (left ? 4u : 0u), g.sh.runs, minus); else bam_cigar<false>(R, q, ops + (left ? 4u : 0u), g.sh.runs, minus);
+        bam_bases(sink.T, sink.M, o + seq_at, o + qual_at, primary ? 0u : g.qs, primary ? g.L : g.qe, minus);
     }
+    /* the same record as the primary: SEQ and QUAL are the whole read, CO:Z:; the operations stay as many (S for H) */
+    if constexpr (!S::write) if (g.top) sink.surplus = bam_bases_bytes(g.L) - bam_bases_bytes(g.qcols) + 4u + comment;
     R.at += bytes;
 }
 
@@ -220,16 +187,9 @@ __global__ void __launch_bounds__(64) k_bam_size(BrxDev d, const RS *rs, const P
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
     PafRead R; R.at = 0; R.best = 0; R.top = 0; R.n_rec = 0; R.frag = nullptr;
-    BamCount<TAGS, F> k_; k_.fmt = F ? fmt : 0u; k_.A.tab = nullptr; k_.A.n = 0; k_.A.sum = 0; k_.out = nullptr; k_.surplus = 0; k_.max_ops = max_ops; k_.M = sam_of(s, nullptr, arena); k_.T.fwd = k_.T.rev = 0;
+    BamSink<false, TAGS, F> k_; sink_init(k_, nullptr, sam_of(s, nullptr, arena), fmt); k_.max_ops = max_ops; k_.T.fwd = k_.T.rev = 0;
     if (paf_has_records(s)) paf_read(k_, d, s, r, segs, arena, R);
-    uint32_t bytes = (uint32_t)R.at + k_.surplus, top = R.top;
-    if (R.n_rec == 0) { top = BRX_SAM_UNMAPPED; bytes = s.rec_len ? bam_unmapped_bytes(s.seq_len, sam_comment(k_)) : 0u; }
-    if (TAGS & BRX_TAG_SA) {
-        const uint32_t n = R.n_rec >= 2 ? R.n_rec : 0u;
-        bytes += n * BRX_BAM_ZTAG + (n ? n - 1u : 0u) * k_.A.sum;
-        if (lane_id() == 0) n_rec[r] = n;
-    }
-    if (lane_id() == 0) { len[r] = bytes; best[r] = top; }
+    truth_size_store(k_, R, r, s.rec_len ? bam_unmapped_bytes(s.seq_len, sam_comment(k_)) : 0u, BRX_BAM_ZTAG, len, best, n_rec);
 }
 
 template <uint32_t TAGS, bool F>
@@ -239,10 +199,10 @@ __global__ void __launch_bounds__(64) k_bam_write(BrxDev d, const RS *rs, const 
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
     if (s.rec_len == 0) return;
-    BamWrite<TAGS, F> w; w.fmt = F ? fmt : 0u; w.A.tab = nullptr; w.A.n = 0; w.A.sum = 0; w.out = out; w.max_ops = max_ops; w.M = sam_of(s, pieces, arena); w.T = bam_nibbles(d);
+    BamSink<true, TAGS, F> w; sink_init(w, out, sam_of(s, pieces, arena), fmt); w.max_ops = max_ops; w.T = bam_nibbles(d);
     if (best[r] != BRX_SAM_UNMAPPED) {
         PafRead R; R.at = off[r]; R.best = best[r]; R.frag = nullptr;
-        if ((TAGS & BRX_TAG_MD) || F) R.frag = Fbuf + s.F_off;
+        if (w.need_f0) R.frag = Fbuf + s.F_off;
         if (TAGS & BRX_TAG_SA) w.A = sa_read_of(table, rec_off, r);
         paf_read(w, d, s, r, segs, arena, R);
         return;

@@ -17,6 +17,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "brx_kernels.h"
@@ -1274,8 +1275,18 @@ extern "C" int brx_bgzf_device(brx_ctx *c, const void *d_in, size_t n_bytes, voi
 
 /* ---- truth alignments of the last simulate batch: PAF text (brx_paf.h), SAM records (brx_sam.h) or BAM records (brx_bam.h) ---- */
 enum { TRUTH_PAF = 0, TRUTH_SAM = 1, TRUTH_BAM = 2 };
-/* one instantiation of the SAM / BAM kernels per set of tags: 0 is the untagged code, nothing of the tags in its column loops */
-#define TAGGED(tags, LAUNCH) do { switch (tags) { case 0: { LAUNCH(0u); } break; case 1: { LAUNCH(1u); } break; case 2: { LAUNCH(2u); } break; default: { LAUNCH(3u); } break; } } while (0)
+/* f(std::integral_constant<uint32_t, TAGS>, std::bool_constant<F>) for the tags and "some format bit" of a call: one instantiation of the SAM /
+   BAM kernels per pair.  TAGS = 0 is the untagged code, nothing of the tags in its column loops; F = false the code of brx_emit_*_tags,
+   nothing of the formats in it; with F the bits are a value of the grid's. */
+template <class Fn> static void with_tags_fmt(uint32_t tags, bool fmtd, Fn f) {
+    auto with_fmt = [&](auto T) { if (fmtd) f(T, std::true_type{}); else f(T, std::false_type{}); };
+    switch (tags) {
+        case 0: with_fmt(std::integral_constant<uint32_t, 0u>{}); break;
+        case 1: with_fmt(std::integral_constant<uint32_t, 1u>{}); break;
+        case 2: with_fmt(std::integral_constant<uint32_t, 2u>{}); break;
+        default: with_fmt(std::integral_constant<uint32_t, 3u>{}); break;
+    }
+}
 static int emit_truth(brx_ctx *c, int kind, uint32_t fmt, uint32_t tags, uint32_t max_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
     if (!c || !out_bytes) return BRX_E_ARG;
     *out_bytes = 0;
@@ -1301,28 +1312,17 @@ static int emit_truth(brx_ctx *c, int kind, uint32_t fmt, uint32_t tags, uint32_
     uint64_t *off = (uint64_t *)(c->d_paf + off_at), *rec_off = (uint64_t *)(c->d_paf + recoff_at);
     const uint8_t *arena = (const uint8_t *)c->scratch;
     const bool sam = kind == TRUTH_SAM, bam = kind == TRUTH_BAM, sa = (tags & BRX_TAG_SA) != 0;
-    /* and two per set of tags: without format bits (the code of brx_emit_*_tags), and with them as a value of the grid's */
-#define BAM_SIZE_F(T, F) hipLaunchKernelGGL((k_bam_size<T, F>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, max_ops, len, best, n_rec, fmt)
-#define SAM_SIZE_F(T, F) hipLaunchKernelGGL((k_sam_size<T, F>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best, n_rec, fmt)
-#define BAM_SIZE(T) BAM_SIZE_F(T, false)
-#define SAM_SIZE(T) SAM_SIZE_F(T, false)
-#define BAM_SIZE_FMT(T) BAM_SIZE_F(T, true)
-#define SAM_SIZE_FMT(T) SAM_SIZE_F(T, true)
-    if (n && bam && fmt) TAGGED(tags, BAM_SIZE_FMT);
-    else if (n && bam) TAGGED(tags, BAM_SIZE);
-    else if (n && sam && fmt) TAGGED(tags, SAM_SIZE_FMT);
-    else if (n && sam) TAGGED(tags, SAM_SIZE);
-    else if (n && fmt) hipLaunchKernelGGL(k_paf_size_fmt, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, fmt, len, best);
-    else if (n) hipLaunchKernelGGL(k_paf_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best);
-#undef BAM_SIZE_F
-#undef SAM_SIZE_F
-#undef BAM_SIZE
-#undef SAM_SIZE
-#undef BAM_SIZE_FMT
-#undef SAM_SIZE_FMT
-    if (sam || bam) hipLaunchKernelGGL(k_sam_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
-    else hipLaunchKernelGGL(k_paf_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
-    if (sa) hipLaunchKernelGGL(k_sam_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)n_rec, rec_off);
+    const uint64_t *c_off = off, *c_rec_off = rec_off;
+    const uint32_t *c_best = best;
+    auto size = [&](auto T, auto F) {
+        constexpr uint32_t TG = decltype(T)::value; constexpr bool FM = decltype(F)::value;
+        if (bam) hipLaunchKernelGGL((k_bam_size<TG, FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, max_ops, len, best, n_rec, fmt);
+        else if (sam) hipLaunchKernelGGL((k_sam_size<TG, FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best, n_rec, fmt);
+        else hipLaunchKernelGGL((k_paf_size<FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, fmt, len, best);
+    };
+    if (n) with_tags_fmt(tags, fmt != 0, size);
+    hipLaunchKernelGGL(k_truth_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
+    if (sa) hipLaunchKernelGGL(k_truth_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)n_rec, rec_off);
     { int rcw = wait_stream(c, st, bam ? "k_bam_size" : sam ? "k_sam_size" : "k_paf_size"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
     const uint64_t total = ((const uint64_t *)(c->h_paf + off_at))[n];
@@ -1341,28 +1341,17 @@ static int emit_truth(brx_ctx *c, int kind, uint32_t fmt, uint32_t tags, uint32_
     }
     SaRec *table = (SaRec *)c->d_sa;
     if (n && total && sa_recs) hipLaunchKernelGGL(k_sa_fill, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, (const uint64_t *)rec_off, table);
-#define BAM_WRITE_F(T, F) hipLaunchKernelGGL((k_bam_write<T, F>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf, \
-                                        max_ops, (const uint64_t *)off, (const uint32_t *)best, d_out, c->paf_frags, (const uint64_t *)rec_off, (const SaRec *)table, fmt)
-#define SAM_WRITE_F(T, F) hipLaunchKernelGGL((k_sam_write<T, F>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf, \
-                                        (const uint64_t *)off, (const uint32_t *)best, d_out, c->paf_frags, (const uint64_t *)rec_off, (const SaRec *)table, fmt)
-#define BAM_WRITE(T) BAM_WRITE_F(T, false)
-#define SAM_WRITE(T) SAM_WRITE_F(T, false)
-#define BAM_WRITE_FMT(T) BAM_WRITE_F(T, true)
-#define SAM_WRITE_FMT(T) SAM_WRITE_F(T, true)
-    if (n && total && bam && fmt) TAGGED(tags, BAM_WRITE_FMT);
-    else if (n && total && bam) TAGGED(tags, BAM_WRITE);
-    else if (n && total && sam && fmt) TAGGED(tags, SAM_WRITE_FMT);
-    else if (n && total && sam) TAGGED(tags, SAM_WRITE);
-    else if (n && total && fmt) hipLaunchKernelGGL(k_paf_write_fmt, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, c->paf_seqbuf, c->paf_frags, fmt,
-                                                   (const uint64_t *)off, (const uint32_t *)best, d_out);
-    else if (n && total) hipLaunchKernelGGL(k_paf_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena,
-                                            (const uint64_t *)off, (const uint32_t *)best, d_out);
-#undef BAM_WRITE_F
-#undef SAM_WRITE_F
-#undef BAM_WRITE
-#undef SAM_WRITE
-#undef BAM_WRITE_FMT
-#undef SAM_WRITE_FMT
+    const SaRec *c_table = table;
+    auto write = [&](auto T, auto F) {
+        constexpr uint32_t TG = decltype(T)::value; constexpr bool FM = decltype(F)::value;
+        if (bam) hipLaunchKernelGGL((k_bam_write<TG, FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf, max_ops,
+                                    c_off, c_best, d_out, c->paf_frags, c_rec_off, c_table, fmt);
+        else if (sam) hipLaunchKernelGGL((k_sam_write<TG, FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf,
+                                         c_off, c_best, d_out, c->paf_frags, c_rec_off, c_table, fmt);
+        else hipLaunchKernelGGL((k_paf_write<FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, c->paf_seqbuf, c->paf_frags, fmt,
+                                c_off, c_best, d_out);
+    };
+    if (n && total) with_tags_fmt(tags, fmt != 0, write);
     if (d_read_off) HIPCHK(c, hipMemcpyAsync(d_read_off, c->h_paf + off_at, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
     { int rcw = wait_stream(c, st, bam ? "k_bam_write" : sam ? "k_sam_write" : "k_paf_write"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());

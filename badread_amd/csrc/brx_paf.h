@@ -17,13 +17,15 @@
  *   paf_record sizes a record (a sweep over its columns: op counts and the text length of its CIGAR) and, for the writing
  *              sink, writes it (a second sweep: every lane that ends a CIGAR run places its text with a wave prefix sum;
  *              '-' records mirror the runs, the convention of minimap2 that alignment.py undoes)
- * The same code sizes (PafCount) and writes (PafWrite): k_paf_size / k_paf_scan / k_paf_write, the pattern of
+ * The same code sizes and writes (PafSink<WRITE, F>): k_paf_size / k_truth_scan / k_paf_write, the pattern of
  * k_recsize / k_scan_rec / k_emit.  The walk hands every record to its sink (sink.record), so brx_sam.h walks the same records.
+ * Every sweep over a record's columns begins with the same step (run_step): the lane's column, its op, whether it starts or ends
+ * a CIGAR run, and where its run started.
  *
  * brx_emit_paf_fmt (BRX_FMT_*): with BRX_FMT_EQX a CIGAR run is a run of one op instead of one class (template parameter EQX of the
- * sweeps, paf_run), with BRX_FMT_CS a third sweep (cs_sweep) writes minimap2's cs:Z: behind AS:i:.  The sinks PafFmtCount / PafFmtWrite
- * and the kernels k_paf_size_fmt / k_paf_write_fmt carry the bits as a value; PafCount / PafWrite and k_paf_size / k_paf_write hold
- * nothing of them.  brx_sam.h and brx_bam.h use the same sweeps.
+ * sweeps, paf_run), with BRX_FMT_CS a third sweep (cs_sweep) writes minimap2's cs:Z: behind AS:i:.  The sinks and kernels with F
+ * (PafSink<*, true>, k_paf_size<true>, k_paf_write<true>) carry the bits as a value; those without hold nothing of them.
+ * brx_sam.h and brx_bam.h use the same sweeps.
  */
 #ifndef BRX_PAF_H
 #define BRX_PAF_H
@@ -50,23 +52,12 @@ struct PafRead {                                                 /* what a recor
 };
 struct PafShape { uint32_t cnt[4], text, runs; };                /* a record's columns by op, the text length and the runs of its CIGAR */
 
-/* The sinks of the walk (paf_read): what is done with every record it closes.  brx_sam.h adds its own two. */
+/* The sinks of the walk (paf_read): what is done with every record it closes.  brx_sam.h and brx_bam.h add their own. */
 template <class S> __device__ void paf_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q);
-struct PafCount {
-    static constexpr bool write = false, need_f0 = false, fmtd = false; uint8_t *out;
-    __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { paf_record(*this, d, R, q); }
-};
-struct PafWrite {
-    static constexpr bool write = true, need_f0 = false, fmtd = false; uint8_t *out;
-    __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { paf_record(*this, d, R, q); }
-};
-/* brx_emit_paf_fmt: the same two with BRX_FMT_* bits (fmt, uniform over the grid) and the read's kept bases for cs:Z: (seq) */
-struct PafFmtCount {
-    static constexpr bool write = false, need_f0 = true, fmtd = true; uint8_t *out; uint32_t fmt; const uint8_t *seq;
-    __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { paf_record(*this, d, R, q); }
-};
-struct PafFmtWrite {
-    static constexpr bool write = true, need_f0 = true, fmtd = true; uint8_t *out; uint32_t fmt; const uint8_t *seq;
+/* WRITE: sizes or writes.  F: with BRX_FMT_* bits (fmt, uniform over the grid) and the read's kept bases for cs:Z: (seq); without F
+   the two stay unset and unread. */
+template <bool WRITE, bool F> struct PafSink {
+    static constexpr bool write = WRITE, need_f0 = F, fmtd = F; uint8_t *out; uint32_t fmt; const uint8_t *seq;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { paf_record(*this, d, R, q); }
 };
 /* a sink's BRX_FMT_* bits: the constant 0 for the sinks without (fmtd = false), whose code holds nothing of the formats */
@@ -96,30 +87,43 @@ __device__ void paf_tags(B &b, uint32_t nm, int64_t as) {
 template <class B>
 __device__ void paf_tail(B &b, uint32_t nm, int64_t as) { paf_tags(b, nm, as); b.put('\n'); }
 
+/* What every sweep over the record [q.c0, q.c1] begins a 64-column step at b with: the lane's column c (in: inside the record), its op,
+   whether it starts (rs) or ends (re) a run -- of one class, with EQX of one op; beyond the record's ends prev / next are 0xFF, which is
+   no op and no class -- the ballot of the starts, the first column s0 of the lane's own run (run_start: the last start of the steps
+   before) and what the next step takes for run_start.  Every lane calls it. */
+struct RunStep { uint32_t c, op, s0, next_start; bool in, rs, re; uint64_t rmask; };
+template <bool EQX>
+__device__ __forceinline__ RunStep run_step(const PafRead &R, const PafRec &q, uint32_t b, uint32_t run_start) {
+    const int lane = lane_id();
+    RunStep t;
+    t.c = b + lane;
+    t.in = t.c <= q.c1;
+    t.op = t.in ? R.ops[t.c] : 0u;
+    const uint32_t prev = (t.in && t.c > q.c0) ? R.ops[t.c - 1] : 0xFFu;
+    const uint32_t next = (t.in && t.c < q.c1) ? R.ops[t.c + 1] : 0xFFu;
+    t.rs = t.in && paf_run<EQX>(prev) != paf_run<EQX>(t.op);
+    t.re = t.in && paf_run<EQX>(next) != paf_run<EQX>(t.op);
+    t.rmask = __ballot(t.rs);
+    const uint64_t mine = t.rmask & ((2ull << lane) - 1ull);
+    t.s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
+    t.next_start = t.rmask ? b + (uint32_t)paf_top(t.rmask) : run_start;
+    return t;
+}
+/* the n decimal digits of v at p[0, n) */
+__device__ __forceinline__ void put_dec_at(uint8_t *p, uint32_t v, uint32_t n) { for (uint32_t x = n; x-- > 0;) { p[x] = (uint8_t)('0' + v % 10); v /= 10; } }
+
 /* Sweep 1 over the record [q.c0, q.c1]: op counts, the CIGAR's text length and its number of runs.  A lane whose column ends a run (the next column
    is another class, or the record ends) owns that run's text: its decimal length and the letter.  Every lane calls it. */
 template <bool EQX>
 __device__ PafShape paf_shape(const PafRead &R, const PafRec &q) {
-    const int lane = lane_id();
-    const uint64_t below = (1ull << lane) - 1ull;
     PafShape sh; sh.cnt[0] = sh.cnt[1] = sh.cnt[2] = sh.cnt[3] = 0; sh.text = 0; sh.runs = 0;
     uint32_t run_start = q.c0;
     for (uint32_t b = q.c0; b <= q.c1; b += 64) {
-        const uint32_t c = b + lane;
-        const bool in = c <= q.c1;
-        const uint32_t op = in ? R.ops[c] : 0u;
-        const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
-        const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
-        const bool rs = in && (c == q.c0 || paf_run<EQX>(prev) != paf_run<EQX>(op));
-        const bool re = in && (c == q.c1 || paf_run<EQX>(next) != paf_run<EQX>(op));
-        const uint64_t rmask = __ballot(rs);
-        const uint64_t mine = rmask & (below | (1ull << lane));
-        const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
-        const uint32_t t = re ? paf_digits(c - s0 + 1) + 1u : 0u;
-        sh.text += wave_sum(t);
-        sh.runs += (uint32_t)__popcll(rmask);
-        for (uint32_t o = 0; o < 4; ++o) sh.cnt[o] += (uint32_t)__popcll(__ballot(in && op == o));
-        if (rmask) run_start = b + (uint32_t)paf_top(rmask);
+        const RunStep t = run_step<EQX>(R, q, b, run_start);
+        sh.text += wave_sum(t.re ? paf_digits(t.c - t.s0 + 1) + 1u : 0u);
+        sh.runs += (uint32_t)__popcll(t.rmask);
+        for (uint32_t o = 0; o < 4; ++o) sh.cnt[o] += (uint32_t)__popcll(__ballot(t.in && t.op == o));
+        run_start = t.next_start;
     }
     return sh;
 }
@@ -128,32 +132,20 @@ __device__ PafShape paf_shape(const PafRead &R, const PafRec &q) {
    records mirror the runs. */
 template <bool EQX>
 __device__ void paf_cigar(const PafRead &R, const PafRec &q, uint8_t *cig, uint32_t text, bool minus) {
-    const int lane = lane_id();
-    const uint64_t below = (1ull << lane) - 1ull;
     uint32_t done = 0, run_start = q.c0;
     for (uint32_t b = q.c0; b <= q.c1; b += 64) {
-        const uint32_t c = b + lane;
-        const bool in = c <= q.c1;
-        const uint32_t op = in ? R.ops[c] : 0u;
-        const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
-        const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
-        const bool rs = in && (c == q.c0 || paf_run<EQX>(prev) != paf_run<EQX>(op));
-        const bool re = in && (c == q.c1 || paf_run<EQX>(next) != paf_run<EQX>(op));
-        const uint64_t rmask = __ballot(rs);
-        const uint64_t mine = rmask & (below | (1ull << lane));
-        const uint32_t s0 = mine ? b + (uint32_t)paf_top(mine) : run_start;
-        const uint32_t len = c - s0 + 1u;
-        const uint32_t t = re ? paf_digits(len) + 1u : 0u;
+        const RunStep s = run_step<EQX>(R, q, b, run_start);
+        const uint32_t len = s.c - s.s0 + 1u;
+        const uint32_t t = s.re ? paf_digits(len) + 1u : 0u;
         const uint32_t incl = wave_incl_scan(t);
-        if (re) {
+        if (s.re) {
             const uint32_t fwd = done + incl - t;
             uint8_t *p = cig + (minus ? text - fwd - t : fwd);
-            uint32_t v = len;
-            for (uint32_t x = t - 1; x-- > 0;) { p[x] = (uint8_t)('0' + v % 10); v /= 10; }
-            p[t - 1] = paf_letter<EQX>(op);
+            put_dec_at(p, len, t - 1u);
+            p[t - 1] = paf_letter<EQX>(s.op);
         }
         done += wave_bcast_u32(incl, 63);
-        if (rmask) run_start = b + (uint32_t)paf_top(rmask);
+        run_start = s.next_start;
     }
 }
 
@@ -178,16 +170,9 @@ __device__ uint32_t cs_sweep(const BrxDev &d, const PafRead &R, const PafRec &q,
     const uint64_t below = (1ull << lane) - 1ull;
     uint32_t done = 0, run_start = q.c0, f_base = q.f0, r_base = q.r0 - R.start_trim;
     for (uint32_t b = q.c0; b <= q.c1; b += 64) {
-        const uint32_t c = b + lane;
-        const bool in = c <= q.c1;
-        const uint32_t op = in ? R.ops[c] : 0u;
-        const uint32_t prev = (in && c > q.c0) ? R.ops[c - 1] : 0xFFu;
-        const uint32_t next = (in && c < q.c1) ? R.ops[c + 1] : 0xFFu;
-        const bool rs = in && prev != op, re = in && next != op;
-        const bool lead = minus ? re : rs;
-        const uint64_t rmask = __ballot(rs);
-        const uint64_t mine = rmask & (below | (1ull << lane));
-        const uint32_t n = c - (mine ? b + (uint32_t)paf_top(mine) : run_start) + 1u;
+        const RunStep s = run_step<true>(R, q, b, run_start);            /* cs runs are runs of one op, whatever the CIGAR's are */
+        const bool in = s.in, re = s.re, lead = minus ? s.re : s.rs;
+        const uint32_t op = s.op, n = s.c - s.s0 + 1u;
         uint32_t t = 0;
         if (in) t = op == 1u ? 3u : (op == 0u && !lng) ? (re ? 1u + paf_digits(n) : 0u) : 1u + (lead ? 1u : 0u);
         if (!WRITE) done += wave_sum(t);
@@ -202,8 +187,7 @@ __device__ uint32_t cs_sweep(const BrxDev &d, const PafRead &R, const PafRec &q,
                 if (op == 1u) { p[0] = '*'; p[1] = (uint8_t)(rb | 0x20u); p[2] = (uint8_t)(qb | 0x20u); }
                 else if (op == 0u && !lng) {
                     p[0] = ':';
-                    uint32_t v = n;
-                    for (uint32_t x = t - 1u; x > 0; --x) { p[x] = (uint8_t)('0' + v % 10); v /= 10; }
+                    put_dec_at(p + 1, n, t - 1u);
                 } else {
                     if (lead) p[0] = (uint8_t)(op == 0u ? '=' : op == 2u ? '+' : '-');
                     p[t - 1u] = op == 0u ? rb : (uint8_t)((op == 2u ? qb : rb) | 0x20u);
@@ -212,7 +196,7 @@ __device__ uint32_t cs_sweep(const BrxDev &d, const PafRead &R, const PafRec &q,
             done += wave_bcast_u32(incl, 63);
             f_base += (uint32_t)__popcll(tm); r_base += (uint32_t)__popcll(qm);
         }
-        if (rmask) run_start = b + (uint32_t)paf_top(rmask);
+        run_start = s.next_start;
     }
     return WRITE ? text : done;
 }
@@ -343,55 +327,45 @@ __device__ __forceinline__ bool paf_has_records(const RS &s) {
 }
 
 /* bytes and primary record of every read */
-__global__ void __launch_bounds__(64) k_paf_size(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t *len, uint32_t *best) {
+template <bool F>
+__global__ void __launch_bounds__(64) k_paf_size(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t fmt, uint32_t *len, uint32_t *best) {
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
-    PafRead R; R.at = 0; R.best = 0; R.top = 0;
-    if (paf_has_records(s)) { PafCount k_; k_.out = nullptr; paf_read(k_, d, s, r, segs, arena, R); }
+    PafRead R; R.at = 0; R.best = 0; R.top = 0; R.frag = nullptr;
+    if (paf_has_records(s)) { PafSink<false, F> k_; k_.out = nullptr; if constexpr (F) { k_.fmt = fmt; k_.seq = nullptr; } paf_read(k_, d, s, r, segs, arena, R); }
     if (lane_id() == 0) { len[r] = (uint32_t)R.at; best[r] = R.top; }
 }
 
-/* read offsets: off[r] (n_reads + 1 entries, the last = total bytes), and the caller's copy when it asks for one */
-__global__ void __launch_bounds__(64) k_paf_scan(uint32_t n_reads, const uint32_t *len, uint64_t *off) {
+/* read offsets of every truth format, and the SA table's record offsets: off[r] (n_reads + 1 entries, the last = the total); the running
+   sums are 64 bits throughout (a batch's SAM or BAM records may pass 2^32 bytes) */
+__global__ void __launch_bounds__(64) k_truth_scan(uint32_t n_reads, const uint32_t *len, uint64_t *off) {
     const int lane = lane_id();
     uint64_t run = 0;
     for (uint32_t base = 0; base < n_reads; base += 64) {
         const uint32_t r = base + lane;
-        const uint32_t l = r < n_reads ? len[r] : 0u;
-        const uint32_t inc = wave_incl_scan(l);         /* a 64-read group stays far below 2^32 bytes */
+        const uint64_t l = r < n_reads ? len[r] : 0u;
+        uint64_t inc = l;
+#pragma unroll
+        for (int dd = 1; dd < 64; dd <<= 1) {
+            const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)inc, dd, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), dd, 64);
+            if (lane >= dd) inc += ((uint64_t)hi << 32) | lo;
+        }
         if (r < n_reads) off[r] = run + inc - l;
-        run += wave_bcast_u32(inc, 63);
+        run += wave_bcast_u64(inc, 63);
     }
     if (lane == 0) off[n_reads] = run;
 }
 
-__global__ void __launch_bounds__(64) k_paf_write(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, const uint64_t *off,
-                                                   const uint32_t *best, uint8_t *out) {
+/* with F the writing kernel is given the fragments (Fbuf) and the reads' sequences (seqbuf, where k_emit read them) for cs:Z: */
+template <bool F>
+__global__ void __launch_bounds__(64) k_paf_write(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, const uint8_t *seqbuf, const uint8_t *Fbuf,
+                                                   uint32_t fmt, const uint64_t *off, const uint32_t *best, uint8_t *out) {
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
     if (!paf_has_records(s)) return;
-    PafRead R; R.at = off[r]; R.best = best[r];
-    PafWrite w; w.out = out;
-    paf_read(w, d, s, r, segs, arena, R);
-}
-
-/* brx_emit_paf_fmt with fmt != 0: the two kernels above with the format bits; the writing one is given the fragments (Fbuf) and the
-   reads' sequences (seqbuf, where k_emit read them) for cs:Z: */
-__global__ void __launch_bounds__(64) k_paf_size_fmt(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t fmt, uint32_t *len, uint32_t *best) {
-    const uint32_t r = blockIdx.x;
-    const RS s = rs[r];
-    PafRead R; R.at = 0; R.best = 0; R.top = 0; R.frag = nullptr;
-    if (paf_has_records(s)) { PafFmtCount k_; k_.out = nullptr; k_.fmt = fmt; k_.seq = nullptr; paf_read(k_, d, s, r, segs, arena, R); }
-    if (lane_id() == 0) { len[r] = (uint32_t)R.at; best[r] = R.top; }
-}
-
-__global__ void __launch_bounds__(64) k_paf_write_fmt(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, const uint8_t *seqbuf, const uint8_t *Fbuf,
-                                                       uint32_t fmt, const uint64_t *off, const uint32_t *best, uint8_t *out) {
-    const uint32_t r = blockIdx.x;
-    const RS s = rs[r];
-    if (!paf_has_records(s)) return;
-    PafRead R; R.at = off[r]; R.best = best[r]; R.frag = Fbuf + s.F_off;
-    PafFmtWrite w; w.out = out; w.fmt = fmt; w.seq = seqbuf + s.seq_off + s.start_trim;           /* as k_emit reads them */
+    PafRead R; R.at = off[r]; R.best = best[r]; R.frag = F ? Fbuf + s.F_off : nullptr;
+    PafSink<true, F> w; w.out = out;
+    if constexpr (F) { w.fmt = fmt; w.seq = seqbuf + s.seq_off + s.start_trim; }           /* as k_emit reads them */
     paf_read(w, d, s, r, segs, arena, R);
 }
 

@@ -13,7 +13,7 @@
  *
  * The primary is known only when the sizing walk ends, and its line is longer than the same record's supplementary line.  So
  * k_sam_size sizes every record as supplementary and keeps, beside the running best AS, what that record would add as the
- * primary (SamCount.surplus); it reads no SEQ or QUAL byte.  k_sam_write knows the primary from the sizing pass.  One wave per
+ * primary (SamSink.surplus); it reads no SEQ or QUAL byte.  k_sam_write knows the primary from the sizing pass.  One wave per
  * read; lane 0 writes the fixed fields, the wave places the CIGAR runs and copies SEQ and QUAL 64 bytes per step (contiguous
  * stores; on '-' lines the loads run backwards).
  *
@@ -32,6 +32,8 @@
  */
 #ifndef BRX_SAM_H
 #define BRX_SAM_H
+
+#include <type_traits>
 
 #define BRX_SAM_UNMAPPED (~0u)         /* best[r] of a read whose one line is the unmapped one */
 #define BRX_SAM_NAME 36u               /* characters of a read name (put_uuid) */
@@ -109,8 +111,7 @@ __device__ MdShape md_sweep(const BrxDev &d, const PafRead &R, const PafRec &q, 
                 const uint8_t base = d.ref.sym[minus ? d.ref.comp[code] & 15u : code];
                 uint8_t *p = md + (minus ? sh.text - fwd - t : fwd);
                 uint8_t *num = minus ? p + (t - nd) : p;
-                uint32_t v = u;
-                for (uint32_t x = nd; x-- > 0;) { num[x] = (uint8_t)('0' + v % 10); v /= 10; }
+                put_dec_at(num, u, nd);
                 if (minus) { if (last) p[0] = '^'; p[last ? 1 : 0] = base; }
                 else { if (first) p[nd] = '^'; p[t - 1] = base; }
             }
@@ -122,9 +123,7 @@ __device__ MdShape md_sweep(const BrxDev &d, const PafRead &R, const PafRec &q, 
     if (!WRITE) { sh.tail = carry; sh.text = done + paf_digits(carry); }
     else if (lane == 0) {
         const uint32_t nd = paf_digits(sh.tail);
-        uint8_t *num = minus ? md : md + sh.text - nd;
-        uint32_t v = sh.tail;
-        for (uint32_t x = nd; x-- > 0;) { num[x] = (uint8_t)('0' + v % 10); v /= 10; }
+        put_dec_at(minus ? md : md + sh.text - nd, sh.tail, nd);
     }
     return sh;
 }
@@ -199,86 +198,100 @@ __device__ void sa_write(const BrxDev &d, const SaRead &A, uint32_t i, uint32_t 
 }
 
 template <class S> __device__ void sam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q);
-/* F: the sink carries BRX_FMT_* bits (fmt, uniform over the grid); F = false is the code without them */
-template <uint32_t TAGS, bool F> struct SamCount {
-    static constexpr bool write = false, fmtd = F, need_f0 = (TAGS & BRX_TAG_MD) != 0 || F; static constexpr uint32_t tags = TAGS;
-    uint8_t *out; SamRead M; uint32_t surplus, fmt; SaRead A;        /* A.sum: the elements' lengths of the records so far */
+/* WRITE: sizes or writes.  TAGS: BRX_TAG_MD | BRX_TAG_SA.  F: the sink carries BRX_FMT_* bits (fmt, uniform over the grid); F = false is
+   the code without them.  surplus (sizing only): what the best record so far adds as the primary.  A: the read's SA table (sizing: A.sum is
+   the elements' lengths of the records so far). */
+struct NoWord {};
+template <bool WRITE> using SizingWord = std::conditional_t<WRITE, NoWord, uint32_t>;       /* a word that only a sizing sink holds */
+template <bool WRITE, uint32_t TAGS, bool F> struct SamSink {
+    static constexpr bool write = WRITE, fmtd = F, need_f0 = (TAGS & BRX_TAG_MD) != 0 || F; static constexpr uint32_t tags = TAGS;
+    uint8_t *out; SamRead M; [[no_unique_address]] SizingWord<WRITE> surplus; uint32_t fmt; SaRead A;
     __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { sam_record(*this, d, R, q); }
 };
-template <uint32_t TAGS, bool F> struct SamWrite {
-    static constexpr bool write = true, fmtd = F, need_f0 = (TAGS & BRX_TAG_MD) != 0 || F; static constexpr uint32_t tags = TAGS;
-    uint8_t *out; SamRead M; uint32_t fmt; SaRead A;
-    __device__ void record(const BrxDev &d, PafRead &R, const PafRec &q) { sam_record(*this, d, R, q); }
-};
+/* what k_sam_* and k_bam_* set of their sink before the walk */
+template <class S> __device__ __forceinline__ void sink_init(S &k, uint8_t *out, const SamRead &M, uint32_t fmt) {
+    k.out = out; k.M = M; if constexpr (!S::write) k.surplus = 0; k.fmt = S::fmtd ? fmt : 0u; k.A.tab = nullptr; k.A.n = 0; k.A.sum = 0;
+}
 /* the comment's length: the FASTQ header is '@', the name, a blank, the comment and a newline (RS.hdr_len, k_recsize) */
 template <class S> __device__ __forceinline__ uint32_t sam_comment(const S &sink) { return sink.M.s->hdr_len - (BRX_SAM_NAME + 3u); }
-template <uint32_t TAGS, bool F> __device__ __forceinline__ void sink_surplus(SamCount<TAGS, F> &k, uint32_t v) { k.surplus = v; }
-template <uint32_t TAGS, bool F> __device__ __forceinline__ void sink_surplus(SamWrite<TAGS, F> &, uint32_t) {}
 
+/* What a SAM line and a BAM record of the record q share, before their layouts part: the shape of the CIGAR (with BRX_FMT_EQX the =/X one),
+   NM and AS, the query and target columns, the strand, the clips, the record's place among the read's (line; primary; top: the best AS so
+   far, which paf_rank counts in), and the sizes of the tag values -- MD's shape, the text of cs, and of SA the value's length (sa: the line
+   has one; a sized line counts none, its element goes to sink.A.sum and the size kernel adds the read's at the end).  What a tag costs
+   around its value is the caller's.  Every lane calls it (wave-uniform arguments). */
+struct RecGeom {
+    PafShape sh; MdShape md; int64_t as;
+    uint32_t nm, qcols, tspan, L, qs, qe, left, right, line, cs_text, sa_text;
+    bool eqx, cs_long, minus, primary, top, cs, sa;
+};
+template <class S>
+__device__ __forceinline__ RecGeom rec_geom(S &sink, const BrxDev &d, PafRead &R, const PafRec &q) {
+    const uint32_t fmt = sink_fmt(sink);
+    RecGeom g;
+    g.eqx = (fmt & BRX_FMT_EQX) != 0; g.cs_long = (fmt & BRX_FMT_CS_LONG) != 0;
+    g.sh = g.eqx ? paf_shape<true>(R, q) : paf_shape<false>(R, q);
+    g.nm = g.sh.cnt[1] + g.sh.cnt[2] + g.sh.cnt[3];
+    g.as = (int64_t)g.sh.cnt[0] - (int64_t)g.nm;
+    g.qcols = g.sh.cnt[0] + g.sh.cnt[1] + g.sh.cnt[2]; g.tspan = g.sh.cnt[0] + g.sh.cnt[1] + g.sh.cnt[3];
+    g.minus = ((q.key0 >> 32) & 1u) != 0;
+    g.L = R.seq_len; g.qs = q.r0 - R.start_trim; g.qe = g.qs + g.qcols;
+    g.left = g.minus ? g.L - g.qe : g.qs; g.right = g.minus ? g.qs : g.L - g.qe;
+    g.line = R.n_rec;
+    g.primary = S::write && g.line == R.best;
+    g.top = paf_rank(R, g.as);
+    g.md.text = g.md.tail = 0; g.cs_text = g.sa_text = 0; g.cs = g.sa = false;
+    if (S::tags & BRX_TAG_MD) g.md = md_sweep<false>(d, R, q, g.minus, nullptr, g.md);
+    if (S::tags & BRX_TAG_SA) {
+        if (!S::write) sink.A.sum += sa_rec_of(d, R, q, g.sh).len;
+        else if (sink.A.n) { g.sa = true; g.sa_text = sink.A.sum - sink.A.tab[g.line].len; }
+    }
+    if constexpr (S::fmtd) if (fmt & BRX_FMT_CS) { g.cs = true; g.cs_text = cs_sweep<false>(d, R, q, g.minus, g.cs_long, nullptr, nullptr, 0u); }
+    return g;
+}
 
 /* One record of the read as a SAM line: sized (as a supplementary line; the primary's surplus goes with the best AS), or
    written.  Every lane calls it (wave-uniform arguments). */
 template <class S>
 __device__ void sam_record(S &sink, const BrxDev &d, PafRead &R, const PafRec &q) {
-    const uint32_t fmt = sink_fmt(sink);
-    const bool eqx = (fmt & BRX_FMT_EQX) != 0;
-    const PafShape sh = eqx ? paf_shape<true>(R, q) : paf_shape<false>(R, q);
-    const uint32_t nm = sh.cnt[1] + sh.cnt[2] + sh.cnt[3];
-    const int64_t as = (int64_t)sh.cnt[0] - (int64_t)nm;
-    const uint32_t qcols = sh.cnt[0] + sh.cnt[1] + sh.cnt[2], tspan = sh.cnt[0] + sh.cnt[1] + sh.cnt[3];
-    const bool minus = ((q.key0 >> 32) & 1u) != 0;
-    const uint32_t L = R.seq_len, qs = q.r0 - R.start_trim, qe = qs + qcols;
-    const uint32_t left = minus ? L - qe : qs, right = minus ? qs : L - qe;
-    const uint32_t line = R.n_rec;
-    const bool primary = S::write && line == R.best;
-    const bool top = paf_rank(R, as);
-    /* MD:Z: and SA:Z: (a sized line counts no SA: k_sam_size adds the read's at the end) */
-    MdShape md; md.text = md.tail = 0;
-    uint32_t md_len = 0, sa_len = 0;
-    if (S::tags & BRX_TAG_MD) { md = md_sweep<false>(d, R, q, minus, nullptr, md); md_len = BRX_SAM_LEN(BRX_SAM_MD) + md.text; }
-    if (S::tags & BRX_TAG_SA) {
-        if (!S::write) sink.A.sum += sa_rec_of(d, R, q, sh).len;
-        else if (sink.A.n) sa_len = BRX_SAM_LEN(BRX_SAM_SA) + sink.A.sum - sink.A.tab[line].len;
-    }
-    uint32_t cs_text = 0, cs_len = 0;                                                 /* cs:Z: between MD and SA */
-    if constexpr (S::fmtd) if (fmt & BRX_FMT_CS) {
-        cs_text = cs_sweep<false>(d, R, q, minus, (fmt & BRX_FMT_CS_LONG) != 0, nullptr, nullptr, 0u);
-        cs_len = BRX_PAF_CS_LEN + cs_text;
-    }
+    const RecGeom g = rec_geom(sink, d, R, q);
+    const bool primary = g.primary, minus = g.minus;
+    /* MD:Z:, cs:Z: and SA:Z: behind AS:i:, in this order */
+    const uint32_t md_len = (S::tags & BRX_TAG_MD) ? BRX_SAM_LEN(BRX_SAM_MD) + g.md.text : 0u;
+    const uint32_t cs_len = g.cs ? BRX_PAF_CS_LEN + g.cs_text : 0u, sa_len = g.sa ? BRX_SAM_LEN(BRX_SAM_SA) + g.sa_text : 0u;
     CountSink hc; hc.n = 0;
-    sam_head(hc, d, R, q, tspan, primary);
-    CountSink lc; lc.n = 0; sam_clip(lc, left, primary);
-    CountSink rc; rc.n = 0; sam_clip(rc, right, primary);
-    CountSink tc; tc.n = 0; paf_tags(tc, nm, as);
+    sam_head(hc, d, R, q, g.tspan, primary);
+    CountSink lc; lc.n = 0; sam_clip(lc, g.left, primary);
+    CountSink rc; rc.n = 0; sam_clip(rc, g.right, primary);
+    CountSink tc; tc.n = 0; paf_tags(tc, g.nm, g.as);
     const uint32_t comment = sam_comment(sink);
-    const uint32_t bases = primary ? L : qcols;
-    const uint32_t cig_at = hc.n + lc.n, seq_at = cig_at + sh.text + rc.n + BRX_SAM_LEN(BRX_SAM_MATE), tag_at = seq_at + 2u * bases + 1u;
+    const uint32_t bases = primary ? g.L : g.qcols;
+    const uint32_t cig_at = hc.n + lc.n, seq_at = cig_at + g.sh.text + rc.n + BRX_SAM_LEN(BRX_SAM_MATE), tag_at = seq_at + 2u * bases + 1u;
     const uint32_t bytes = tag_at + tc.n + md_len + cs_len + sa_len + (primary ? BRX_SAM_LEN(BRX_SAM_CO) + comment : 0u) + 1u;
     if (S::write) {
         uint8_t *o = sink.out + R.at;
         if (lane_id() == 0) {
             ByteSink h; h.p = o; h.n = 0;
-            sam_head(h, d, R, q, tspan, primary); sam_clip(h, left, primary);
-            ByteSink m; m.p = o + cig_at + sh.text; m.n = 0;
-            sam_clip(m, right, primary); put_str(m, BRX_SAM_MATE);
+            sam_head(h, d, R, q, g.tspan, primary); sam_clip(h, g.left, primary);
+            ByteSink m; m.p = o + cig_at + g.sh.text; m.n = 0;
+            sam_clip(m, g.right, primary); put_str(m, BRX_SAM_MATE);
             ByteSink t; t.p = o + tag_at; t.n = 0;
-            paf_tags(t, nm, as);
-            if (md_len) { put_str(t, BRX_SAM_MD); t.n += md.text; }            /* the values are the wave's, below */
-            if (cs_len) { put_str(t, BRX_PAF_CS); t.n += cs_text; }
-            if (sa_len) { put_str(t, BRX_SAM_SA); t.n += sa_len - BRX_SAM_LEN(BRX_SAM_SA); }
+            paf_tags(t, g.nm, g.as);
+            if (md_len) { put_str(t, BRX_SAM_MD); t.n += g.md.text; }            /* the values are the wave's, below */
+            if (cs_len) { put_str(t, BRX_PAF_CS); t.n += g.cs_text; }
+            if (sa_len) { put_str(t, BRX_SAM_SA); t.n += g.sa_text; }
             if (primary) { put_str(t, BRX_SAM_CO); put_comment(t, d, *sink.M.s, sink.M.pieces); }
             t.put('\n');
         }
-        if (md_len) md_sweep<true>(d, R, q, minus, o + tag_at + tc.n + BRX_SAM_LEN(BRX_SAM_MD), md);
+        if (md_len) md_sweep<true>(d, R, q, minus, o + tag_at + tc.n + BRX_SAM_LEN(BRX_SAM_MD), g.md);
         if constexpr (S::fmtd) if (cs_len)
-            cs_sweep<true>(d, R, q, minus, (fmt & BRX_FMT_CS_LONG) != 0, sink.M.seq, o + tag_at + tc.n + md_len + BRX_PAF_CS_LEN, cs_text);
-        if (sa_len) sa_write(d, sink.A, line, R.best, o + tag_at + tc.n + md_len + cs_len + BRX_SAM_LEN(BRX_SAM_SA));
-        if (eqx) paf_cigar<true>(R, q, o + cig_at, sh.text, minus); else paf_cigar<false>(R, q, o + cig_at, sh.text, minus);
-        sam_bases(d, sink.M, o + seq_at, primary ? 0u : qs, primary ? L : qe, minus);
-    } else if (top) {
-        /* the same record as the primary: FLAG loses its 2048 (4 digits -> "0" or "16"), SEQ and QUAL are the whole read, CO:Z: */
-        sink_surplus(sink, 2u * (L - qcols) + BRX_SAM_LEN(BRX_SAM_CO) + comment - (minus ? 2u : 3u));
+            cs_sweep<true>(d, R, q, minus, g.cs_long, sink.M.seq, o + tag_at + tc.n + md_len + BRX_PAF_CS_LEN, g.cs_text);
+        if (sa_len) sa_write(d, sink.A, g.line, R.best, o + tag_at + tc.n + md_len + cs_len + BRX_SAM_LEN(BRX_SAM_SA));
+        if (g.eqx) paf_cigar<true>(R, q, o + cig_at, g.sh.text, minus); else paf_cigar<false>(R, q, o + cig_at, g.sh.text, minus);
+        sam_bases(d, sink.M, o + seq_at, primary ? 0u : g.qs, primary ? g.L : g.qe, minus);
     }
+    /* the same record as the primary: FLAG loses its 2048 (4 digits -> "0" or "16"), SEQ and QUAL are the whole read, CO:Z: */
+    if constexpr (!S::write) if (g.top) sink.surplus = 2u * (g.L - g.qcols) + BRX_SAM_LEN(BRX_SAM_CO) + comment - (minus ? 2u : 3u);
     R.at += bytes;
 }
 
@@ -294,23 +307,32 @@ __device__ __forceinline__ SamRead sam_of(const RS &s, const PPiece *pieces, con
     return M;
 }
 
-/* bytes and primary record (BRX_SAM_UNMAPPED: none) of every read; with SA its records in the table too (n_rec: 0 below two) */
+/* The end of k_sam_size and k_bam_size: the bytes and the primary record (BRX_SAM_UNMAPPED: none) of read r.  A read without a record takes
+   `unmapped` bytes; with SA every line of a read of two or more gets the tag (`sa_tag`: what it costs around its value) and the elements of
+   the n - 1 others, and the read's records are counted into the table (n_rec: 0 below two). */
+template <class S>
+__device__ __forceinline__ void truth_size_store(const S &k, const PafRead &R, uint32_t r, uint32_t unmapped, uint32_t sa_tag, uint32_t *len, uint32_t *best,
+                                                 uint32_t *n_rec) {
+    uint32_t bytes = (uint32_t)R.at + k.surplus, top = R.top;
+    if (R.n_rec == 0) { top = BRX_SAM_UNMAPPED; bytes = unmapped; }
+    if (S::tags & BRX_TAG_SA) {
+        const uint32_t n = R.n_rec >= 2 ? R.n_rec : 0u;
+        bytes += n * sa_tag + (n ? n - 1u : 0u) * k.A.sum;
+        if (lane_id() == 0) n_rec[r] = n;
+    }
+    if (lane_id() == 0) { len[r] = bytes; best[r] = top; }
+}
+
+/* bytes and primary record of every read, SA's record counts */
 template <uint32_t TAGS, bool F>
 __global__ void __launch_bounds__(64) k_sam_size(BrxDev d, const RS *rs, const PSeg *segs, const uint8_t *arena, uint32_t *len, uint32_t *best,
                                                   uint32_t *n_rec, uint32_t fmt) {
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
     PafRead R; R.at = 0; R.best = 0; R.top = 0; R.n_rec = 0; R.frag = nullptr;
-    SamCount<TAGS, F> k_; k_.out = nullptr; k_.surplus = 0; k_.fmt = F ? fmt : 0u; k_.M = sam_of(s, nullptr, arena); k_.A.tab = nullptr; k_.A.n = 0; k_.A.sum = 0;
+    SamSink<false, TAGS, F> k_; sink_init(k_, nullptr, sam_of(s, nullptr, arena), fmt);
     if (paf_has_records(s)) paf_read(k_, d, s, r, segs, arena, R);
-    uint32_t bytes = (uint32_t)R.at + k_.surplus, top = R.top;
-    if (R.n_rec == 0) { top = BRX_SAM_UNMAPPED; bytes = s.rec_len ? sam_unmapped_bytes(s.seq_len, sam_comment(k_)) : 0u; }
-    if (TAGS & BRX_TAG_SA) {
-        const uint32_t n = R.n_rec >= 2 ? R.n_rec : 0u;               /* every line: the tag and the elements of the n - 1 others */
-        bytes += n * BRX_SAM_LEN(BRX_SAM_SA) + (n ? n - 1u : 0u) * k_.A.sum;
-        if (lane_id() == 0) n_rec[r] = n;
-    }
-    if (lane_id() == 0) { len[r] = bytes; best[r] = top; }
+    truth_size_store(k_, R, r, s.rec_len ? sam_unmapped_bytes(s.seq_len, sam_comment(k_)) : 0u, BRX_SAM_LEN(BRX_SAM_SA), len, best, n_rec);
 }
 
 /* the SA table: one SaRec per record of every read that the sizing pass counted in (rec_off: the scan of its n_rec) */
@@ -323,25 +345,6 @@ __global__ void __launch_bounds__(64) k_sa_fill(BrxDev d, const RS *rs, const PS
     paf_read(f_, d, s, r, segs, arena, R);
 }
 
-/* read offsets: off[r] (n_reads + 1 entries, the last = total bytes); the running sums are 64 bits throughout */
-__global__ void __launch_bounds__(64) k_sam_scan(uint32_t n_reads, const uint32_t *len, uint64_t *off) {
-    const int lane = lane_id();
-    uint64_t run = 0;
-    for (uint32_t base = 0; base < n_reads; base += 64) {
-        const uint32_t r = base + lane;
-        const uint64_t l = r < n_reads ? len[r] : 0u;
-        uint64_t inc = l;
-#pragma unroll
-        for (int dd = 1; dd < 64; dd <<= 1) {
-            const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)inc, dd, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(inc >> 32), dd, 64);
-            if (lane >= dd) inc += ((uint64_t)hi << 32) | lo;
-        }
-        if (r < n_reads) off[r] = run + inc - l;
-        run += wave_bcast_u64(inc, 63);
-    }
-    if (lane == 0) off[n_reads] = run;
-}
-
 template <uint32_t TAGS, bool F>
 __global__ void __launch_bounds__(64) k_sam_write(BrxDev d, const RS *rs, const PSeg *segs, const PPiece *pieces, const uint8_t *arena,
                                                    const uint64_t *off, const uint32_t *best, uint8_t *out, const uint8_t *Fbuf,
@@ -349,10 +352,10 @@ __global__ void __launch_bounds__(64) k_sam_write(BrxDev d, const RS *rs, const 
     const uint32_t r = blockIdx.x;
     const RS s = rs[r];
     if (s.rec_len == 0) return;
-    SamWrite<TAGS, F> w; w.fmt = F ? fmt : 0u; w.out = out; w.M = sam_of(s, pieces, arena); w.A.tab = nullptr; w.A.n = 0; w.A.sum = 0;
+    SamSink<true, TAGS, F> w; sink_init(w, out, sam_of(s, pieces, arena), fmt);
     if (best[r] != BRX_SAM_UNMAPPED) {
         PafRead R; R.at = off[r]; R.best = best[r]; R.frag = nullptr;
-        if ((TAGS & BRX_TAG_MD) || F) R.frag = Fbuf + s.F_off;
+        if (w.need_f0) R.frag = Fbuf + s.F_off;
         if (TAGS & BRX_TAG_SA) w.A = sa_read_of(table, rec_off, r);
         paf_read(w, d, s, r, segs, arena, R);
         return;

@@ -84,6 +84,8 @@ PAF_SHARE = 0.1
 SAM_SHARE = 1.5
 # --truth-bam: the same for a batch's BAM records before they are compressed (measured 1.14 on configs[3]: profiles/truth_bam.md)
 BAM_SHARE = 1.2
+TRUTH_KINDS = ('paf', 'sam', 'bam')      # the truth files, in the order a driver makes and ships them
+TRUTH_SHARE = dict(paf=PAF_SHARE, sam=SAM_SHARE, bam=BAM_SHARE)
 # --truth-tags: what MD:Z: / SA:Z: add to a batch's SAM or BAM records, per FASTQ byte (measured 0.0574-0.0578 and 0.0097-0.0099 on
 # configs[3], the same within 0.0003 in BAM: profiles/truth_tags.md; MD grows with the error rate, and E_OUTPUT's retry is behind it)
 TAG_MD, TAG_SA = 1, 2                  # include/brx.h: BRX_TAG_MD, BRX_TAG_SA
@@ -316,20 +318,12 @@ def bind_library(lib):
                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
     lib.brx_model_count.restype = ctypes.c_int
     lib.brx_model_count.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(BrxModelJob), ctypes.c_void_p]
-    lib.brx_emit_paf.restype = ctypes.c_int
-    lib.brx_emit_paf.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t),
-                                 ctypes.c_void_p]
-    lib.brx_emit_sam.restype = ctypes.c_int
-    lib.brx_emit_sam.argtypes = lib.brx_emit_paf.argtypes
-    lib.brx_emit_bam.restype = ctypes.c_int
-    lib.brx_emit_bam.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + list(lib.brx_emit_paf.argtypes[1:])
-    lib.brx_emit_sam_tags.restype = ctypes.c_int
-    lib.brx_emit_sam_tags.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + list(lib.brx_emit_paf.argtypes[1:])
-    lib.brx_emit_bam_tags.restype = ctypes.c_int
-    lib.brx_emit_bam_tags.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32] + list(lib.brx_emit_paf.argtypes[1:])
-    for name, extra in (('brx_emit_paf_fmt', 1), ('brx_emit_sam_fmt', 2), ('brx_emit_bam_fmt', 3)):       # fmt; tags; max_cigar_ops
+    # brx_emit_*: the context, so many uint32 of their own (fmt, tags, max_cigar_ops in the order of include/brx.h), then the same five
+    emit_tail = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
+    for name, words in (('brx_emit_paf', 0), ('brx_emit_sam', 0), ('brx_emit_bam', 1), ('brx_emit_sam_tags', 1), ('brx_emit_bam_tags', 2),
+                        ('brx_emit_paf_fmt', 1), ('brx_emit_sam_fmt', 2), ('brx_emit_bam_fmt', 3)):
         getattr(lib, name).restype = ctypes.c_int
-        getattr(lib, name).argtypes = [ctypes.c_void_p] + [ctypes.c_uint32] * extra + list(lib.brx_emit_paf.argtypes[1:])
+        getattr(lib, name).argtypes = [ctypes.c_void_p] + [ctypes.c_uint32] * words + emit_tail
     lib.brx_bgzf_device_bound.restype = ctypes.c_size_t
     lib.brx_bgzf_device_bound.argtypes = [ctypes.c_size_t]
     lib.brx_bgzf_device_scratch.restype = ctypes.c_size_t
@@ -577,35 +571,27 @@ class HipEngine(EngineBase):
         stats = self._stats[:n_reads * READ_STATS_DTYPE.itemsize].cpu().numpy().view(READ_STATS_DTYPE)
         return self._out[:nbytes], stats
 
+    def emit_truth_device(self, kind, n_reads, tags=0, fmt=0, max_cigar_ops=65535):
+        """Truth alignments of the last simulate_batch(_device) of this engine, which had `n_reads` reads, as `kind`: 'paf' (PAF text), 'sam'
+        (SAM records, no header) or 'bam' (uncompressed BAM records, no header, one per SAM line) -- include/brx.h, brx_emit_<kind>_fmt.
+        Returns (device uint8 tensor of the records in read order, numpy uint64 offsets of each read's records, n_reads + 1 entries).  The
+        tensor is a fresh one: the engine may take its next batch at once.  The kinds may be asked for one batch in any order.
+        `fmt`: FMT_EQX | FMT_CS | FMT_CS_LONG, =/X CIGAR runs and a cs:Z: behind AS.  `tags` (SAM, BAM): TAG_MD | TAG_SA adds MD:Z: / SA:Z:.
+        `max_cigar_ops` (BAM): a record with more CIGAR operations takes the CG:B:I form."""
+        words = {'paf': (fmt,), 'sam': (fmt, tags), 'bam': (fmt, tags, max_cigar_ops)}[kind]
+        entry = getattr(self.lib, f'brx_emit_{kind}_fmt')
+        share = TRUTH_SHARE[kind] + (tag_share(tags) if kind != 'paf' else 0.0) + fmt_share(fmt, kind)
+        return self._emit_truth(lambda ctx, *rest: entry(ctx, *map(int, words), *rest), share, n_reads)
+
+    # emit_truth_device by the names and positional arguments that tools and tests call
     def emit_paf_device(self, n_reads, fmt=0):
-        """Truth alignments (PAF text, include/brx.h brx_emit_paf) of the last simulate_batch(_device) of this engine, which had
-        `n_reads` reads: (device uint8 tensor of the records in read order, numpy uint64 offsets of each read's records, n_reads + 1
-        entries).  The tensor is a fresh one: the engine may take its next batch at once.  `fmt`: FMT_EQX | FMT_CS | FMT_CS_LONG, =/X
-        runs in cg:Z: and a cs:Z: behind AS (brx_emit_paf_fmt)."""
-        if not fmt:
-            return self._emit_truth(self.lib.brx_emit_paf, PAF_SHARE, n_reads)
-        emit = lambda ctx, *rest: self.lib.brx_emit_paf_fmt(ctx, int(fmt), *rest)
-        return self._emit_truth(emit, PAF_SHARE + fmt_share(fmt, 'paf'), n_reads)
+        return self.emit_truth_device('paf', n_reads, fmt=fmt)
 
     def emit_sam_device(self, n_reads, tags=0, fmt=0):
-        """The same truth as SAM records (include/brx.h brx_emit_sam; no header), with emit_paf_device's arguments and results.
-        Both may be called for one batch, in either order.  `tags`: TAG_MD | TAG_SA adds MD:Z: / SA:Z: (brx_emit_sam_tags); `fmt` as for
-        emit_paf_device (brx_emit_sam_fmt)."""
-        if not fmt:
-            emit = lambda ctx, *rest: self.lib.brx_emit_sam_tags(ctx, int(tags), *rest)
-        else:
-            emit = lambda ctx, *rest: self.lib.brx_emit_sam_fmt(ctx, int(fmt), int(tags), *rest)
-        return self._emit_truth(emit, SAM_SHARE + tag_share(tags) + fmt_share(fmt, 'sam'), n_reads)
+        return self.emit_truth_device('sam', n_reads, tags, fmt)
 
     def emit_bam_device(self, n_reads, max_cigar_ops=65535, tags=0, fmt=0):
-        """The same truth as uncompressed BAM records (include/brx.h brx_emit_bam; no header), one per SAM line, with
-        emit_paf_device's arguments and results.  A record with more than `max_cigar_ops` CIGAR operations takes the CG:B:I form;
-        `tags` and `fmt` as for emit_sam_device (brx_emit_bam_tags, brx_emit_bam_fmt)."""
-        if not fmt:
-            emit = lambda ctx, *rest: self.lib.brx_emit_bam_tags(ctx, int(tags), int(max_cigar_ops), *rest)
-        else:
-            emit = lambda ctx, *rest: self.lib.brx_emit_bam_fmt(ctx, int(fmt), int(tags), int(max_cigar_ops), *rest)
-        return self._emit_truth(emit, BAM_SHARE + tag_share(tags) + fmt_share(fmt, 'bam'), n_reads)
+        return self.emit_truth_device('bam', n_reads, tags, fmt, max_cigar_ops)
 
     def bgzf_device(self, data):
         """brx_bgzf_device: a uint8 tensor on this engine's device -> a uint8 tensor (same device) holding BGZF blocks of it, one per

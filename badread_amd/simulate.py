@@ -34,7 +34,8 @@ import time
 import numpy as np
 
 from . import settings
-from .engine import BAM_SHARE, PAF_SHARE, SAM_SHARE, fmt_share, tag_share, RS_BAND, RS_NOFRAG, RS_QMISS, RS_TOO_MANY_SEGS, SimParams
+# BAM_SHARE, PAF_SHARE and SAM_SHARE are not used here: tests and tools read them as simulate.PAF_SHARE and the like
+from .engine import BAM_SHARE, PAF_SHARE, SAM_SHARE, TRUTH_KINDS, TRUTH_SHARE, fmt_share, tag_share, RS_BAND, RS_NOFRAG, RS_QMISS, RS_TOO_MANY_SEGS, SimParams
 from .error_model import ErrorModel
 from .fragment_lengths import FragmentLengths
 from .identities import Identities
@@ -360,16 +361,39 @@ def kept_bytes(stats, first, base, last, n_mine):
     return keep, (int(stats['rec_off'][keep - 1] + stats['rec_len'][keep - 1]) if keep else 0)
 
 
-def expected_out_bytes(engine, n_reads, mean_length, truth_paf, truth_sam=False, truth_bam=False, truth_tags=0, truth_fmt=0):
-    """Bytes a batch of `n_reads` reads is expected to leave on the device (with --truth-paf its PAF text, with --truth-sam its SAM records,
-    with --truth-bam its BAM records before they are compressed too, with --truth-tags what the tags add to either, with --truth-cs /
-    --truth-eqx what they add to each of the three): by the engine's estimate
+class TruthSpec(collections.namedtuple('TruthSpec', 'kinds tags fmt')):
+    """What truth output a job writes beside its FASTQ: `kinds`, the files (--truth-paf, --truth-sam, --truth-bam) as a subset of
+    ('paf', 'sam', 'bam') in that order, which is the order their records are made and shipped in; `tags` (--truth-tags), TAG_MD | TAG_SA
+    on the SAM and BAM records; `fmt` (--truth-eqx, --truth-cs), FMT_EQX | FMT_CS | FMT_CS_LONG on all three.  TruthSpec.NONE: none."""
+    __slots__ = ()
+
+    def __new__(cls, kinds=(), tags=0, fmt=0):
+        asked = set(kinds)
+        return super().__new__(cls, tuple(k for k in TRUTH_KINDS if k in asked), int(tags), int(fmt))
+
+    @classmethod
+    def from_args(cls, args):
+        return cls([k for k in TRUTH_KINDS if getattr(args, 'truth_' + k, None)], getattr(args, 'truth_tags', None) or 0,
+                   getattr(args, 'truth_fmt', None) or 0)
+
+    def share(self):
+        """Bytes of truth records per FASTQ byte that a batch's buffers are first sized for: every file's own share, what the tags add to
+        the SAM and the BAM records, what the formats add to each file."""
+        share = sum(TRUTH_SHARE[k] for k in self.kinds)
+        share += tag_share(self.tags) * sum(k != 'paf' for k in self.kinds)
+        return share + sum(fmt_share(self.fmt, k) for k in self.kinds)
+
+
+TruthSpec.NONE = TruthSpec()
+
+
+def expected_out_bytes(engine, n_reads, mean_length, truth=None):
+    """Bytes a batch of `n_reads` reads is expected to leave on the device, the truth records of `truth` (a TruthSpec) included -- the BAM
+    records before they are compressed too: by the engine's estimate
     from its parameters, or at 2.1 B per base + 400 per read for an engine without one (None: its parameters are not set yet)."""
     per_read = engine.expected_record_bytes() if hasattr(engine, 'expected_record_bytes') else 2.1 * mean_length + 400.0
     out_bytes = int(n_reads * per_read)
-    share = (PAF_SHARE if truth_paf else 0.0) + (SAM_SHARE if truth_sam else 0.0) + (BAM_SHARE if truth_bam else 0.0)
-    share += tag_share(truth_tags) * (bool(truth_sam) + bool(truth_bam))
-    share += sum(fmt_share(truth_fmt, kind) for kind, on in (('paf', truth_paf), ('sam', truth_sam), ('bam', truth_bam)) if on)
+    share = (truth or TruthSpec.NONE).share()
     return int(out_bytes * (1.0 + share)) if share else out_bytes
 
 
@@ -520,7 +544,7 @@ class _ArenaPrefetch(object):
             pass
 
     @staticmethod
-    def for_job(engine, target_size, mean_length, error_rate, in_flight, world, truth_paf=False, truth_sam=False, truth_bam=False, truth_tags=0, truth_fmt=0):
+    def for_job(engine, target_size, mean_length, error_rate, in_flight, world, truth=None):
         """Arenas for the batches in flight of THIS job on THIS device, or None (not a GPU engine, a job of one small batch,
         BRX_ARENA_PREFETCH=0).  How many: what the job will use and the free memory holds (engines_for_memory, no arena mapped yet)."""
         # Measured (profiles/r05i_arena_prefetch.json, r05k_*; DESIGN.md has the figures): the read loop then runs undisturbed, 18.8-19.0 s for
@@ -533,7 +557,7 @@ class _ArenaPrefetch(object):
         if first_batch < 4096:
             return None                                  # a small job: one arena, sized by presize
         nbytes = engine.arena_bytes(first_batch, mean_length, error_rate) if hasattr(engine, 'arena_bytes') else arena_estimate(first_batch, mean_length, error_rate)
-        out_bytes = expected_out_bytes(None, first_batch, mean_length, truth_paf, truth_sam, truth_bam, truth_tags, truth_fmt)        # the engine's parameters are not set yet
+        out_bytes = expected_out_bytes(None, first_batch, mean_length, truth)        # the engine's parameters are not set yet
         batches = -(-int(target_size) // max(int(first_batch * mean_length * max(world, 1)), 1))
         free, _ = engine.torch.cuda.mem_get_info(engine.device)
         n = engines_for_memory(free, max(1, min(int(in_flight), batches)), nbytes, 0, out_bytes, driver_reserve_bytes())
@@ -546,6 +570,11 @@ class _Done(object):
     def result(self): return self.v
 
 
+# What a worker hands back: the FASTQ bytes, the stats, (text bytes, gzip members) or None, and per truth file
+# {kind: (records or their BGZF blocks, read offsets into the records, whether these are the blocks)} -- {} for a batch of no reads
+_Batch = collections.namedtuple('_Batch', 'out stats packed truth')
+
+
 class _BatchPool(object):
     """`in_flight` engines (the given one + clones sharing its device tables), each driven by its own host thread on its own HIP stream, so that
     several batches overlap on the GPU.
@@ -556,15 +585,12 @@ class _BatchPool(object):
     bytes device-to-device out of the engine's buffer when the batch is done (2 GB at HBM speed: ~1 ms) and gives the engine back at once; `depth` =
     in_flight + 2 batches may be outstanding, the surplus holding only their bytes."""
 
-    def __init__(self, engine, in_flight, arenas=None, device_gzip=False, truth_paf=False, truth_sam=False, truth_bam=False, truth_tags=0, truth_fmt=0):
+    def __init__(self, engine, in_flight, arenas=None, device_gzip=False, truth=None):
         self.arenas = arenas
-        self.truth_paf = bool(truth_paf)                 # --truth-paf: every batch's truth alignments, made by its worker beside its FASTQ
-        self.truth_sam = bool(truth_sam)                 # --truth-sam: the same as SAM records
-        # --truth-bam: the same as BAM records, which the worker of a batch that the stop rule cannot cut (submit(..., pack=True)) also compresses
-        # whole into BGZF blocks on its engine's stream; any other batch's are compressed by the consumer, for the reads it keeps
-        self.truth_bam = bool(truth_bam)
-        self.truth_tags = int(truth_tags)                # --truth-tags: TAG_MD | TAG_SA on the SAM and BAM records
-        self.truth_fmt = int(truth_fmt)                  # --truth-eqx / --truth-cs: FMT_EQX | FMT_CS | FMT_CS_LONG on the PAF, SAM and BAM records
+        # the truth files: every batch's truth alignments, made by its worker beside its FASTQ.  The BAM records of a batch that the stop rule
+        # cannot cut (submit(..., pack=True)) are also compressed whole into BGZF blocks by the worker, on its engine's stream; any other
+        # batch's are compressed by the consumer, for the reads it keeps
+        self.truth = truth or TruthSpec.NONE
         # --gzip-device: the worker of a batch that the stop rule cannot cut (submit(..., pack=True)) packs ITS batch on ITS engine's stream and hands
         # over the gzip members; the consumer packs only the job's last batches (every batch there: 10.4 s of configs[4]'s read loop against 6.0 s)
         self.device_gzip = bool(device_gzip)
@@ -640,8 +666,7 @@ class _BatchPool(object):
         return self.pool.submit(self._work, seed, first, n_mine, pack)
 
     def _work(self, seed, first, n_mine, pack):
-        """One batch on the next free engine, on a worker thread: (FASTQ bytes, stats, (text bytes, gzip members) or None, PAF or None, SAM or None,
-        BAM or None); BAM = (records or their BGZF blocks, read offsets into the records, whether these are the blocks)."""
+        """One batch on the next free engine, on a worker thread: a _Batch."""
         import torch
         t_q = time.perf_counter()
         i = self.free.get()
@@ -651,20 +676,15 @@ class _BatchPool(object):
         try:
             stream, eng = self.streams[i], self.engines[i]
             if n_mine == 0:
-                return torch.zeros(0, dtype=torch.uint8), np.zeros(0, dtype=eng.stats_dtype), None, None, None, None
+                return _Batch(torch.zeros(0, dtype=torch.uint8), np.zeros(0, dtype=eng.stats_dtype), None, {})
             if not self.on_gpu:
                 out, stats = eng.simulate_batch(seed, first, n_mine, allow_nofrag=True)
-                paf = self._paf_of(eng, n_mine, self.truth_fmt) if self.truth_paf else None
-                sam = self._sam_of(eng, n_mine, self.truth_tags, self.truth_fmt) if self.truth_sam else None
-                bam = self._bam_of(eng, n_mine, pack, self.truth_tags, self.truth_fmt) if self.truth_bam else None
-                return torch.from_numpy(np.ascontiguousarray(out).copy()), stats.copy(), None, paf, sam, bam
+                return _Batch(torch.from_numpy(np.ascontiguousarray(out).copy()), stats.copy(), None, self._truth_of(eng, n_mine, pack))
             torch.cuda.set_device(eng.device)
             with torch.cuda.stream(stream):
                 out, stats = eng.simulate_batch_device(seed, first, n_mine, allow_nofrag=True)
                 # the truth alignments read what the batch left in the engine's arena: same job, same stream, before the engine is free
-                paf = self._paf_of(eng, n_mine, self.truth_fmt) if self.truth_paf else None
-                sam = self._sam_of(eng, n_mine, self.truth_tags, self.truth_fmt) if self.truth_sam else None
-                bam = self._bam_of(eng, n_mine, pack, self.truth_tags, self.truth_fmt) if self.truth_bam else None
+                truth = self._truth_of(eng, n_mine, pack)
                 stats = stats.copy()
                 packed = None
                 if pack and self.device_gzip and len(stats) and hasattr(eng, 'gzip_device'):
@@ -676,34 +696,22 @@ class _BatchPool(object):
                         packed = (nbytes, eng.gzip_device(out[:nbytes], blocks))      # a new tensor, made on this batch's stream
                 out = self._copy_of(torch, out) if packed is None else None   # the engine's buffer is free again; the copy runs on this batch's stream ...
                 stream.synchronize()                     # ... and is complete before the engine is handed to the next batch
-                return out, stats, packed, paf, sam, bam
+                return _Batch(out, stats, packed, truth)
         finally:
             with self.lock:
                 self.job_seconds += time.perf_counter() - t_job
                 self.job_count += 1
             self.free.put(i)
 
-    @staticmethod
-    def _paf_of(eng, n_mine, fmt=0):
-        """The batch's PAF records and read offsets (an engine is asked for formats only when there are some)."""
-        return eng.emit_paf_device(n_mine, fmt=fmt) if fmt else eng.emit_paf_device(n_mine)
-
-    @staticmethod
-    def _sam_of(eng, n_mine, tags=0, fmt=0):
-        """The batch's SAM records and read offsets (an engine is asked for tags and formats only when there are some)."""
-        kw = dict(tags=tags) if tags else {}
-        if fmt: kw['fmt'] = fmt
-        return eng.emit_sam_device(n_mine, **kw)
-
-    @staticmethod
-    def _bam_of(eng, n_mine, pack, tags=0, fmt=0):
-        """The batch's BAM records and read offsets; with `pack` the records' BGZF blocks instead, made at once on the same stream."""
-        kw = dict(tags=tags) if tags else {}
-        if fmt: kw['fmt'] = fmt
-        data, off = eng.emit_bam_device(n_mine, **kw)
-        if pack and int(data.numel()):
-            return eng.bgzf_device(data), off, True
-        return data, off, False
+    def _truth_of(self, eng, n_mine, pack):
+        """{kind: (the batch's records of that kind, their read offsets, False)}; with `pack` BAM's are (the records' BGZF blocks, made at
+        once on the same stream, the read offsets into the records, True)."""
+        truth = {}
+        for kind in self.truth.kinds:
+            data, off = eng.emit_truth_device(kind, n_mine, tags=self.truth.tags, fmt=self.truth.fmt)
+            packed = kind == 'bam' and pack and int(data.numel()) > 0
+            truth[kind] = (eng.bgzf_device(data) if packed else data, off, packed)
+        return truth
 
     def close(self):
         for th in self.makers[:self.started]:            # clones no batch asked for were never started
@@ -716,8 +724,7 @@ class _BatchPool(object):
 
 
 def run_batches(engine, seed, target_size, mean_length, write, output, shard=None, max_batch=None, in_flight=1, device_gzip=False,
-                local_write=None, local_parts=None, expected_error=None, arenas=None, truth_paf=False, paf_write=None,
-                truth_sam=False, sam_write=None, truth_bam=False, bam_write=None, truth_tags=0, truth_fmt=0):
+                local_write=None, local_parts=None, expected_error=None, arenas=None, truth=None, truth_write=None):
     """
     The `while total_size < target_size` loop (simulate.py:63-86) over super-batches of read indices.
     `write(bytes_like)` receives the FASTQ bytes in read order on rank 0 only.  Returns (read count, total bases).
@@ -739,26 +746,18 @@ def run_batches(engine, seed, target_size, mean_length, write, output, shard=Non
     super-batch, which is what puts the ranks' files back into read order (batch by batch, rank after rank).  The
     exchange of 4 bytes per read and the stop rule are the same: the same reads are kept.
 
-    truth_paf (--truth-paf): every batch also yields its reads' truth alignments (engine.emit_paf_device), cut at the same
-    read as the FASTQ.  `paf_write` receives them in read order: on rank 0, over the same point-to-point exchange as the
-    FASTQ, or with local_write on every rank, its own reads' records (those of its own FASTQ file, in that file's order).
-
-    truth_sam / sam_write (--truth-sam): the same for the reads' SAM records (engine.emit_sam_device), through a ring of their
-    own.  The @ lines of the file are the caller's (sam_header).
-
-    truth_bam / bam_write (--truth-bam): the same records in BAM's binary form (engine.emit_bam_device), cut at the same read and then
-    compressed on the GPU into BGZF blocks (engine.bgzf_device); only the blocks cross to the host, through a ring of their own, and
-    between ranks.  A batch the stop rule cannot cut is compressed whole by its worker.  Header and EOF block are the caller's.
-
-    truth_tags (--truth-tags): TAG_MD | TAG_SA, the tags the SAM and the BAM records carry beside NM and AS.
-
-    truth_fmt (--truth-eqx, --truth-cs): FMT_EQX | FMT_CS | FMT_CS_LONG, =/X CIGAR runs and cs:Z: on the PAF, SAM and BAM records.
+    truth (a TruthSpec) / truth_write ({kind: callable}): every batch also yields its reads' truth alignments in every kind of the spec
+    (engine.emit_truth_device), cut at the same read as the FASTQ.  `truth_write[kind]` receives them in read order through a ring of its
+    own: on rank 0, over the same point-to-point exchange as the FASTQ, or with local_write on every rank, its own reads' records (those
+    of its own FASTQ file, in that file's order).  The @ lines of a SAM file are the caller's (sam_header).  The BAM records are cut at
+    the same read and then compressed on the GPU into BGZF blocks (engine.bgzf_device); only the blocks cross to the host and between
+    ranks.  A batch the stop rule cannot cut is compressed whole by its worker.  Header and EOF block are the caller's.
 
     A sink that fails on one rank of a multi-rank run (a full disk, a closed pipe) is reported in the same exchange -- one
     word per rank -- so that every rank leaves the loop at the same batch instead of waiting in a collective.
     """
     run = _Run(engine, seed, target_size, mean_length, write, output, shard or Shard(), max_batch or DEFAULT_MAX_BATCH, in_flight,
-               device_gzip, local_write, local_parts, expected_error, arenas, truth_paf, paf_write, truth_sam, sam_write, truth_bam, bam_write, truth_tags, truth_fmt)
+               device_gzip, local_write, local_parts, expected_error, arenas, truth or TruthSpec.NONE, truth_write or {})
     run_batches.last_timing = run.timing
     run.size_pipeline()
     run.open_rings()
@@ -780,20 +779,18 @@ class _Run(object):
     (Shard.gather_words, collect_bytes) and every pool.submit comes at a point that depends only on consumed totals: the ranks stay in step."""
 
     def __init__(self, engine, seed, target_size, mean_length, write, output, shard, max_batch, in_flight, device_gzip,
-                 local_write, local_parts, expected_error, arenas, truth_paf, paf_write, truth_sam=False, sam_write=None,
-                 truth_bam=False, bam_write=None, truth_tags=0, truth_fmt=0):
+                 local_write, local_parts, expected_error, arenas, truth, truth_write):
         import torch
         self.torch = torch
         self.engine, self.seed, self.target_size, self.write, self.output, self.shard = engine, seed, target_size, write, output, shard
         self.max_batch, self.in_flight, self.device_gzip, self.expected_error, self.arenas = max_batch, in_flight, device_gzip, expected_error, arenas
-        self.local_write, self.local_parts, self.truth_paf, self.paf_write = local_write, local_parts, truth_paf, paf_write
-        self.truth_sam, self.sam_write = truth_sam, sam_write
-        self.truth_bam, self.bam_write, self.truth_tags, self.truth_fmt = truth_bam, bam_write, int(truth_tags), int(truth_fmt)
+        self.local_write, self.local_parts, self.truth, self.truth_write = local_write, local_parts, truth, truth_write
         self.count = self.total = self.next_read = 0
         self.expected_mean = float(mean_length)
         self.pending = collections.deque()          # _Pending, in index order
         self.fatal, self.bad_read, self.sink_failed_on = False, None, None
-        self.pool = self.ring = self.paf_ring = self.sam_ring = self.bam_ring = self.gz_engine = None
+        self.pool = self.ring = self.gz_engine = None
+        self.truth_rings = {}                       # {kind: _HostRing} of the truth files this rank writes
         if shard.rank == 0:
             print_progress(0, 0, target_size, output)
         self.timing = collections.Counter()         # seconds of the consumer thread per activity (bench.py --d2h)
@@ -810,8 +807,7 @@ class _Run(object):
                 engine.adopt_scratch(first_arena)
             else:                                    # by the job's identity law, if given: arenas for Q30 reads are half those of 95 % reads
                 engine.presize(first_batch, self.expected_mean, self.expected_error)
-            out_bytes = expected_out_bytes(engine, first_batch, self.expected_mean, self.truth_paf, self.truth_sam, self.truth_bam, self.truth_tags,
-                                           self.truth_fmt)
+            out_bytes = expected_out_bytes(engine, first_batch, self.expected_mean, self.truth)
         asked = fit = max(1, int(self.in_flight))
         if first_arena is not None:
             fit = min(fit, arenas.count)             # decided when the arenas were requested, by the same rule, from the memory that was free then
@@ -821,8 +817,7 @@ class _Run(object):
             fit = min(shard.gather_word(fit))
         if fit < asked and shard.rank == 0:
             print(f'  {fit} of the {asked} batches in flight asked for fit into the free device memory', file=self.output)
-        self.pool = _BatchPool(engine, fit, arenas, device_gzip=self.device_gzip, truth_paf=self.truth_paf, truth_sam=self.truth_sam,
-                               truth_bam=self.truth_bam, truth_tags=self.truth_tags, truth_fmt=self.truth_fmt)
+        self.pool = _BatchPool(engine, fit, arenas, device_gzip=self.device_gzip, truth=self.truth)
         self.timing['create_engines'] = time.perf_counter() - self.t_job
 
     def open_rings(self):
@@ -831,15 +826,11 @@ class _Run(object):
         pinned, defer = self.pool.on_gpu, self.shard.world > 1
         if self.local_write is not None or self.shard.rank == 0:
             self.ring = _HostRing(self.torch, pinned, self.local_write if self.local_write is not None else self.write, defer)
-        if self.truth_paf and self.paf_write is not None:
-            self.paf_ring = _HostRing(self.torch, pinned, self.paf_write, defer)
-        if self.truth_sam and self.sam_write is not None:
-            self.sam_ring = _HostRing(self.torch, pinned, self.sam_write, defer)
-        if self.truth_bam and self.bam_write is not None:
-            self.bam_ring = _HostRing(self.torch, pinned, self.bam_write, defer)
+        self.truth_rings = {kind: _HostRing(self.torch, pinned, self.truth_write[kind], defer)
+                            for kind in self.truth.kinds if self.truth_write.get(kind) is not None}
         if self.device_gzip and not hasattr(self.engine, 'gzip_device'):
             sys.exit('Error: --gzip-device needs the GPU engine')
-        if self.device_gzip or self.truth_bam:
+        if self.device_gzip or 'bam' in self.truth.kinds:
             self.gz_engine = self.engine.clone(1 << 20) if hasattr(self.engine, 'clone') else self.engine      # its own context: the others are busy
 
     def staging(self, nbytes):
@@ -859,20 +850,20 @@ class _Run(object):
             first, n_mine = self.shard.slice_of(self.next_read, n_super)
             # --gzip-device: a batch with at least three batches' worth of bases still to come behind it is kept whole
             # (--truth-bam: the same batches' BAM records are compressed whole by their workers)
-            pack = (self.device_gzip or self.truth_bam) and remaining > 4.0 * n_super * self.expected_mean
+            pack = (self.device_gzip or 'bam' in self.truth.kinds) and remaining > 4.0 * n_super * self.expected_mean
             self.pending.append(_Pending(self.pool.submit(self.seed, first, n_mine, pack=pack), self.next_read, n_super, first, n_mine))
             self.next_read += n_super
 
     def consume(self, batch):
         """The next super-batch in index order: wait, exchange, decide, pack, account, refill, ship.  False: the loop ends here."""
         timing, shard, t0 = self.timing, self.shard, time.perf_counter()
-        out, stats, prepacked, paf, sam, bam = batch.future.result()
+        out, stats, prepacked, truth = batch.future.result()
         timing['wait_for_batch'] += time.perf_counter() - t0
         timing['batches'] += 1
         allw = exchange_words(stats)
-        if shard.world > 1:                         # every rank's words in read order, and one more of each rank: "my sink has failed" (FASTQ's, PAF's or SAM's)
+        if shard.world > 1:                         # every rank's words in read order, and one more of each rank: "my sink has failed" (the FASTQ's or a truth file's)
             per_rank = [Shard(r, shard.world).slice_of(batch.base, batch.n_super)[1] for r in range(shard.world)]
-            failed_here = any(x is not None and x.error is not None for x in (self.ring, self.paf_ring, self.sam_ring, self.bam_ring))
+            failed_here = any(x is not None and x.error is not None for x in (self.ring, *self.truth_rings.values()))
             parts = shard.gather_words(np.append(allw, np.uint32(1 if failed_here else 0)), [c + 1 for c in per_rank])
             failed = [r for r, part in enumerate(parts) if part[-1]]
             if failed:                              # every rank leaves here, at the same batch
@@ -899,23 +890,21 @@ class _Run(object):
         self.ship(self.ring, out, my_bytes, sizes)
         if local and self.local_parts is not None:
             self.local_parts(my_bytes)
-        if self.truth_paf:                          # the records of the same reads, the same way
-            paf_bytes, paf_sizes = int(paf[1][keep]) if paf is not None else 0, None
+        # The truth records of the same reads, the same way, file after file.  PAF's sizes travel as 32-bit words like the FASTQ's; a
+        # super-batch's SAM records may pass 2^32 bytes on a rank, and BAM's leave as BGZF blocks: whole blocks of every rank, so rank 0
+        # only concatenates
+        for kind in self.truth.kinds:
+            part = truth.get(kind)                  # None: no reads of this batch on this rank
+            if kind == 'bam':
+                data = self.pack_bam(part, keep)
+                nbytes = int(data.numel()) if data is not None else 0
+            else:
+                data, nbytes = (part[0], int(part[1][keep])) if part is not None else (None, 0)
+            kind_sizes = None
             if shard.world > 1 and not local:
-                paf_sizes = shard.gather_word(paf_bytes)
-                assert paf_bytes < 2 ** 32
-            self.ship(self.paf_ring, paf[0] if paf is not None else None, paf_bytes, paf_sizes)
-        if self.truth_sam:                          # and their SAM records: a super-batch's may pass 2^32 bytes on a rank
-            sam_bytes, sam_sizes = int(sam[1][keep]) if sam is not None else 0, None
-            if shard.world > 1 and not local:
-                sam_sizes = shard.gather_word64(sam_bytes)
-            self.ship(self.sam_ring, sam[0] if sam is not None else None, sam_bytes, sam_sizes)
-        if self.truth_bam:                          # and their BAM records, as BGZF blocks: whole blocks of every rank, so rank 0 only concatenates
-            blocks = self.pack_bam(bam, keep)
-            bam_bytes, bam_sizes = int(blocks.numel()) if blocks is not None else 0, None
-            if shard.world > 1 and not local:
-                bam_sizes = shard.gather_word64(bam_bytes)
-            self.ship(self.bam_ring, blocks, bam_bytes, bam_sizes)
+                kind_sizes = shard.gather_word(nbytes) if kind == 'paf' else shard.gather_word64(nbytes)
+                assert kind != 'paf' or nbytes < 2 ** 32
+            self.ship(self.truth_rings.get(kind), data, nbytes, kind_sizes)
         timing['copy_out'] += time.perf_counter() - t0
         if shard.rank == 0:
             print_progress(self.count, self.total, self.target_size, self.output)
@@ -998,9 +987,8 @@ class _Run(object):
             self.ring.flush(reraise=not quiet and not self.ring.defer_errors)
             timing['sink'] = self.ring.sink_seconds
             timing['ring_alloc'] = self.ring.alloc_seconds
-        for ring in (self.paf_ring, self.sam_ring, self.bam_ring):
-            if ring is not None:
-                ring.flush(reraise=not quiet and not ring.defer_errors)
+        for ring in self.truth_rings.values():
+            ring.flush(reraise=not quiet and not ring.defer_errors)
         timing['flush'] = time.perf_counter() - t0
         timing['retries'] = sum(getattr(e, 'retries', 0) for e in pool.engines if e is not None)
         timing['device_batch_seconds_avg'] = pool.job_seconds / max(pool.job_count, 1.0)
@@ -1014,7 +1002,7 @@ class _Run(object):
 
     def raise_outcome(self):
         """The ways out other than a count: this rank's own sink, another rank's sink, no fragment, a read beyond the GPU path's limits."""
-        for ring in (self.ring, self.paf_ring, self.sam_ring, self.bam_ring):      # this rank's own sink, then its own PAF, SAM and BAM files
+        for ring in (self.ring, *self.truth_rings.values()):      # this rank's own sink, then its own PAF, SAM and BAM files
             if ring is not None and ring.error is not None and (self.sink_failed_on is not None or ring.defer_errors):
                 raise ring.error
         if self.sink_failed_on is not None:
@@ -1070,12 +1058,12 @@ class _PartsLog(object):
 
 class _Outputs(object):
     """Where a rank's bytes go (open_outputs): `write` to rank 0's stdout (through --gzip's sink if asked for); with --output-shards
-    `local_write` and `local_parts`, this rank's own file and parts log; with --truth-paf `paf_write`, with --truth-sam `sam_write`, with
-    --truth-bam `bam_write`.  None where not in use."""
-    local_write = local_parts = paf_write = sam_write = bam_write = None
+    `local_write` and `local_parts`, this rank's own file and parts log (None where not in use); `truth_write`, {kind: the write of this
+    rank's --truth-<kind> file}."""
+    local_write = local_parts = None
 
     def __init__(self, sink):
-        self.sink, self.files, self.bam_files = sink, [], []
+        self.sink, self.files, self.bam_files, self.truth_write = sink, [], [], {}
 
     def write(self, part):
         if self.sink is not None:
@@ -1139,46 +1127,34 @@ def open_outputs(args, shard, engine, stdout, pref=None):
             shard_sink.write(memoryview(part))
             log.wrote(len(part))
         outs.local_write, outs.local_parts = local_write, log.batch
-    # --truth-paf PATH: the truth alignments of the reads (brx_emit_paf), plain text; with --output-shards every rank writes
-    # PATH.<rank>, the records of the reads of its own FASTQ file
-    truth_paf = getattr(args, 'truth_paf', None)
-    if truth_paf:
-        if not hasattr(engine, 'emit_paf_device'):
+    # --truth-paf PATH: the truth alignments of the reads (brx_emit_paf), plain text; with --output-shards every rank writes PATH.<rank>, the
+    # records of the reads of its own FASTQ file.  --truth-sam PATH: the same as SAM (brx_emit_sam), the same files; each begins with the
+    # header, which depends on the reference alone.  --truth-bam PATH: the same header and records as BAM; the host writes the header's BGZF
+    # blocks and, on closing, the EOF block
+    from .output import bam_header, bgzf_host
+    # kind; what every rank makes of the reference first (ValueError: an exit all ranks take alike); what the file begins with, made of that
+    for kind, checked, header in (('paf', None, None), ('sam', None, sam_header), ('bam', bam_header, bgzf_host)):
+        path = getattr(args, 'truth_' + kind, None)
+        if not path:
+            continue
+        if not hasattr(engine, 'emit_truth_device'):
             shard.finish()
-            sys.exit('Error: --truth-paf needs the GPU engine')
+            sys.exit(f'Error: --truth-{kind} needs the GPU engine')
+        first = pref
+        if checked is not None:
+            try:
+                first = checked(pref)
+            except ValueError as ex:           # every rank alike: it depends on the reference alone
+                shard.finish()
+                sys.exit(f'Error: --truth-{kind}: {ex}')
         if prefix or shard.rank == 0:
-            paf_file = open(f'{truth_paf}.{shard.rank}' if prefix else truth_paf, 'wb')
-            outs.files.append(paf_file)
-            outs.paf_write = paf_file.write
-    # --truth-sam PATH: the same as SAM (brx_emit_sam), the same files; each begins with the header, which depends on the reference alone
-    truth_sam = getattr(args, 'truth_sam', None)
-    if truth_sam:
-        if not hasattr(engine, 'emit_sam_device'):
-            shard.finish()
-            sys.exit('Error: --truth-sam needs the GPU engine')
-        if prefix or shard.rank == 0:
-            sam_file = open(f'{truth_sam}.{shard.rank}' if prefix else truth_sam, 'wb')
-            outs.files.append(sam_file)
-            sam_file.write(sam_header(pref))
-            outs.sam_write = sam_file.write
-    # --truth-bam PATH: the same header and records as BAM; the host writes the header's BGZF blocks and, on closing, the EOF block
-    truth_bam = getattr(args, 'truth_bam', None)
-    if truth_bam:
-        if not hasattr(engine, 'emit_bam_device'):
-            shard.finish()
-            sys.exit('Error: --truth-bam needs the GPU engine')
-        from .output import bam_header, bgzf_host
-        try:
-            header = bam_header(pref)
-        except ValueError as ex:               # every rank alike: it depends on the reference alone
-            shard.finish()
-            sys.exit(f'Error: --truth-bam: {ex}')
-        if prefix or shard.rank == 0:
-            bam_file = open(f'{truth_bam}.{shard.rank}' if prefix else truth_bam, 'wb')
-            outs.files.append(bam_file)
-            outs.bam_files.append(bam_file)
-            bam_file.write(bgzf_host(header))
-            outs.bam_write = bam_file.write
+            f = open(f'{path}.{shard.rank}' if prefix else path, 'wb')
+            outs.files.append(f)
+            if kind == 'bam':
+                outs.bam_files.append(f)
+            if header is not None:
+                f.write(header(first))
+            outs.truth_write[kind] = f.write
     return outs
 
 
@@ -1223,13 +1199,11 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
     _, cum_weight = pref.contig_weights(depths)
     engine.set_reference(pref, cum_weight)
     mark('reference_on_device')
-    truth_tags = int(getattr(args, 'truth_tags', None) or 0)                     # --truth-tags: TAG_MD | TAG_SA (check_simulate_args)
-    truth_fmt = int(getattr(args, 'truth_fmt', None) or 0)                       # --truth-eqx, --truth-cs: FMT_EQX | FMT_CS | FMT_CS_LONG
+    truth = TruthSpec.from_args(args)
     # the job's arenas from now on, beside everything below (models, tables, the first batch): _ArenaPrefetch
     arenas = _ArenaPrefetch.for_job(engine, get_target_size(pref.n_bases, args.quantity), float(args.mean_frag_length),
                                     expected_error_rate(identities), getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, shard.world,
-                                    truth_paf=bool(getattr(args, 'truth_paf', None)), truth_sam=bool(getattr(args, 'truth_sam', None)),
-                                    truth_bam=bool(getattr(args, 'truth_bam', None)), truth_tags=truth_tags, truth_fmt=truth_fmt)
+                                    truth=truth)
     # a model file that is not in the cache is aligned (align_kmers, error_model.py:179-229) on THIS engine
     error_model = ErrorModel(args.error_model, quiet, aligner=lambda qs, ts: engine.align_batch(qs, ts)[0])
     qscore_model = QScoreModel(args.qscore_model, quiet)
@@ -1255,10 +1229,7 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
             result = run_batches(engine, seed, target_size, float(args.mean_frag_length), outs.write, quiet, shard,
                                  in_flight=getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, device_gzip=bool(getattr(args, 'gzip_device', False)),
                                  local_write=outs.local_write, local_parts=outs.local_parts, expected_error=expected_error_rate(identities),
-                                 arenas=arenas, truth_paf=bool(getattr(args, 'truth_paf', None)), paf_write=outs.paf_write,
-                                 truth_sam=bool(getattr(args, 'truth_sam', None)), sam_write=outs.sam_write,
-                                 truth_bam=bool(getattr(args, 'truth_bam', None)), bam_write=outs.bam_write, truth_tags=truth_tags,
-                                 truth_fmt=truth_fmt)
+                                 arenas=arenas, truth=truth, truth_write=outs.truth_write)
         finally:
             outs.close()
     except (SystemExit, OSError):

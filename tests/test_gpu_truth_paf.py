@@ -142,7 +142,7 @@ def test_truth_paf_models_equal_the_restatement_at_scale(tmp_path):
 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # one full device batch of configs[3] at the shipped geometry (tests/test_gpu_fullsize.py builds it the same way): long reads,
-# many 64-column steps and records per read, every band class and route of the final stage, k_paf_scan over 65 536 reads
+# many 64-column steps and records per read, every band class and route of the final stage, k_truth_scan over 65 536 reads
 
 _CIGAR = re.compile(rb'(\d+)([MID])')
 

@@ -271,10 +271,10 @@ def test_driver_reserve_and_expected_out_bytes(monkeypatch):
         def expected_record_bytes(self):
             return 34000.0
     # an engine without an estimate of its own (and None): 2.1 B per base + 400 per read
-    assert S.expected_out_bytes(object(), 1000, 15000.0, False) == S.expected_out_bytes(None, 1000, 15000.0, False) == 31900000
-    assert S.expected_out_bytes(Knows(), 1000, 15000.0, False) == 34000000
-    assert S.expected_out_bytes(Knows(), 1000, 15000.0, True) == int(34000000 * (1.0 + PAF_SHARE))
-    assert S.expected_out_bytes(None, 4096, 15000.0, True) == int(4096 * (2.1 * 15000.0 + 400.0) * (1.0 + PAF_SHARE))
+    assert S.expected_out_bytes(object(), 1000, 15000.0, S.TruthSpec.NONE) == S.expected_out_bytes(None, 1000, 15000.0) == 31900000
+    assert S.expected_out_bytes(Knows(), 1000, 15000.0, None) == 34000000
+    assert S.expected_out_bytes(Knows(), 1000, 15000.0, S.TruthSpec(['paf'])) == int(34000000 * (1.0 + PAF_SHARE))
+    assert S.expected_out_bytes(None, 4096, 15000.0, S.TruthSpec(['paf'])) == int(4096 * (2.1 * 15000.0 + 400.0) * (1.0 + PAF_SHARE))
     assert S.Shard().gather_word(7) == [7] and not S._on_gpu(object()) and not S._on_gpu(None)
 
 
@@ -547,3 +547,61 @@ def test_device_copies_of_a_batch_come_in_size_steps(monkeypatch):
     assert caps == {8192}
     small = torch.arange(100, dtype=torch.uint8)
     assert _BatchPool._copy_of(torch, small).untyped_storage().nbytes() == 100      # small batches: a plain clone
+
+
+TRUTH_COMBINATIONS = [(p, s, b) for p in (None, 'x.paf') for s in (None, 'x.sam') for b in (None, 'x.bam')]
+
+
+@pytest.mark.parametrize('paf,sam,bam', TRUTH_COMBINATIONS)
+def test_truth_spec_reads_the_arguments_and_sums_the_shares(paf, sam, bam):
+    """TruthSpec.from_args: the files asked for, always in the order paf, sam, bam, with the tags and the formats; share(): every file's
+    share, the tags' once per SAM and BAM file, the formats' once per file -- the sum written out from engine's constants."""
+    from badread_amd import engine as E
+    want = tuple(k for k, path in (('paf', paf), ('sam', sam), ('bam', bam)) if path)
+    spec = S.TruthSpec.from_args(Args(truth_bam=bam, truth_paf=paf, truth_sam=sam))
+    assert spec == (want, 0, 0) and spec.kinds == want and (spec == S.TruthSpec.NONE) == (not want)
+    assert S.TruthSpec.from_args(Args()) == S.TruthSpec.NONE == S.TruthSpec() and S.TruthSpec.NONE.share() == 0
+    assert S.TruthSpec(reversed(want), 1, 2) == S.TruthSpec(want, 1, 2) == (want, 1, 2)           # the order is the class's, not the caller's
+    for tags, fmt in ((0, 0), (E.TAG_MD, 0), (E.TAG_MD | E.TAG_SA, E.FMT_EQX), (0, E.FMT_CS), (E.TAG_SA, E.FMT_EQX | E.FMT_CS | E.FMT_CS_LONG)):
+        spec = S.TruthSpec.from_args(Args(truth_paf=paf, truth_sam=sam, truth_bam=bam, truth_tags=tags, truth_fmt=fmt))
+        assert spec == (want, tags, fmt)
+        share = (E.PAF_SHARE if paf else 0.0) + (E.SAM_SHARE if sam else 0.0) + (E.BAM_SHARE if bam else 0.0)
+        share += ((E.MD_SHARE if tags & E.TAG_MD else 0.0) + (E.SA_SHARE if tags & E.TAG_SA else 0.0)) * (bool(sam) + bool(bam))
+        for kind in want:
+            cs = (E.CS_LONG_SHARE if fmt & E.FMT_CS_LONG else E.CS_SHORT_SHARE)[kind] if fmt & E.FMT_CS else 0.0
+            share += (E.EQX_SHARE[kind] if fmt & E.FMT_EQX else 0.0) + cs
+        assert spec.share() == pytest.approx(share, rel=1e-15, abs=0)
+        base = 1000 * (2.1 * 15000.0 + 400.0)
+        assert S.expected_out_bytes(None, 1000, 15000.0, spec) == pytest.approx(base * (1.0 + share), abs=1.5)
+
+
+def test_a_worker_makes_every_truth_kind_in_order():
+    """_BatchPool with the three files: the worker asks its engine for paf, sam and bam in this order, with the job's tags and formats, and
+    hands each kind's records back under its name; a batch that cannot be cut has its BAM records compressed by the worker, and only those."""
+    import torch
+    calls = []
+
+    class Eng(object):
+        stats_dtype = np.dtype([('x', 'u4')])
+        def simulate_batch(self, seed, first, n, allow_nofrag=True):
+            return np.zeros(4, dtype=np.uint8), np.zeros(n, dtype=self.stats_dtype)
+        def emit_truth_device(self, kind, n, tags=0, fmt=0, max_cigar_ops=65535):
+            calls.append((kind, n, tags, fmt, max_cigar_ops))
+            return torch.tensor(list(kind.encode()), dtype=torch.uint8), np.array([0, 1, 3], dtype=np.uint64)
+        def bgzf_device(self, data):
+            return torch.cat([torch.tensor([31, 139], dtype=torch.uint8), data])
+
+    pool = S._BatchPool(Eng(), 1, truth=S.TruthSpec(('bam', 'paf', 'sam'), 3, 5))
+    got = pool.submit(1, 0, 2).result()
+    assert got._fields == ('out', 'stats', 'packed', 'truth') and got.packed is None and len(got.stats) == 2
+    assert calls == [('paf', 2, 3, 5, 65535), ('sam', 2, 3, 5, 65535), ('bam', 2, 3, 5, 65535)]
+    assert list(got.truth) == ['paf', 'sam', 'bam']
+    for kind, (data, off, packed) in got.truth.items():
+        assert bytes(data.numpy()) == kind.encode() and list(off) == [0, 1, 3] and packed is False
+    packed = pool.submit(1, 2, 2, pack=True).result().truth
+    assert [(k, bytes(v[0].numpy()), v[2]) for k, v in packed.items()] == [('paf', b'paf', False), ('sam', b'sam', False), ('bam', b'\x1f\x8bbam', True)]
+    assert pool.submit(1, 4, 0).result().truth == {} and len(calls) == 6             # no reads here: nothing is asked for
+    one = S._BatchPool(Eng(), 1, truth=S.TruthSpec(['sam']))
+    assert list(one.submit(1, 0, 2).result().truth) == ['sam'] and calls[-1] == ('sam', 2, 0, 0, 65535)
+    assert S._BatchPool(Eng(), 1).submit(1, 0, 2).result().truth == {}
+    pool.close()

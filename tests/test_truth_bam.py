@@ -289,5 +289,5 @@ def test_truth_bam_needs_the_gpu_engine(tmp_path):
 
 def test_the_bam_share_is_counted_into_the_expected_bytes():
     from badread_amd import simulate as S
-    assert S.expected_out_bytes(None, 1000, 15000.0, False, False, True) == int(1000 * (2.1 * 15000.0 + 400.0) * (1.0 + S.BAM_SHARE))
-    assert S.expected_out_bytes(None, 1000, 15000.0, True, True, True) == int(1000 * (2.1 * 15000.0 + 400.0) * (1.0 + S.PAF_SHARE + S.SAM_SHARE + S.BAM_SHARE))
+    assert S.expected_out_bytes(None, 1000, 15000.0, S.TruthSpec(['bam'])) == int(1000 * (2.1 * 15000.0 + 400.0) * (1.0 + S.BAM_SHARE))
+    assert S.expected_out_bytes(None, 1000, 15000.0, S.TruthSpec(['paf', 'sam', 'bam'])) == int(1000 * (2.1 * 15000.0 + 400.0) * (1.0 + S.PAF_SHARE + S.SAM_SHARE + S.BAM_SHARE))

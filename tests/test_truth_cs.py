@@ -266,7 +266,9 @@ def test_the_first_buffer_counts_every_share_once_per_file():
     base = 1000 * (2.1 * 15000.0 + 400.0)
     for share in (E.EQX_SHARE, E.CS_SHORT_SHARE, E.CS_LONG_SHARE):
         assert sorted(share) == ['bam', 'paf', 'sam'] and all(v > 0 for v in share.values())
-    bytes_of = lambda *a, **kw: S.expected_out_bytes(None, 1000, 15000.0, *a, **kw)
+    def bytes_of(paf, sam, bam, tags, fmt=0, truth_fmt=0):             # the flags as the driver reads them off its arguments
+        kinds = [k for k, on in (('paf', paf), ('sam', sam), ('bam', bam)) if on]
+        return S.expected_out_bytes(None, 1000, 15000.0, S.TruthSpec(kinds, tags, fmt or truth_fmt))
     near = lambda share: pytest.approx(base * (1.0 + share), abs=1.5)       # int() of a sum of doubles taken in another order
     assert bytes_of(True, True, True, 3) == bytes_of(True, True, True, 3, truth_fmt=0) == bytes_of(True, True, True, 3, 0)
     assert bytes_of(False, True, False, 3, truth_fmt=3) == near(S.SAM_SHARE + E.MD_SHARE + E.SA_SHARE + E.EQX_SHARE['sam'] + E.CS_SHORT_SHARE['sam'])

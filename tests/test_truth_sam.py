@@ -274,5 +274,5 @@ def test_truth_sam_missing_directory_is_an_error(tmp_path):
 def test_byte_counts_beyond_32_bits_are_exchanged_whole():
     from badread_amd import simulate as S
     assert S.Shard().gather_word64(5 * 2 ** 32 + 7) == [5 * 2 ** 32 + 7]
-    assert S.expected_out_bytes(None, 1000, 15000.0, False, True) == int(1000 * (2.1 * 15000.0 + 400.0) * (1.0 + S.SAM_SHARE))
-    assert S.expected_out_bytes(None, 1000, 15000.0, True, True) == int(1000 * (2.1 * 15000.0 + 400.0) * (1.0 + S.PAF_SHARE + S.SAM_SHARE))
+    assert S.expected_out_bytes(None, 1000, 15000.0, S.TruthSpec(['sam'])) == int(1000 * (2.1 * 15000.0 + 400.0) * (1.0 + S.SAM_SHARE))
+    assert S.expected_out_bytes(None, 1000, 15000.0, S.TruthSpec(['paf', 'sam'])) == int(1000 * (2.1 * 15000.0 + 400.0) * (1.0 + S.PAF_SHARE + S.SAM_SHARE))

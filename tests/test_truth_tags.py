@@ -192,9 +192,9 @@ def test_the_first_buffer_counts_the_tags_once_per_file():
     from badread_amd import engine as E
     from badread_amd import simulate as S
     base = 1000 * (2.1 * 15000.0 + 400.0)
-    assert S.expected_out_bytes(None, 1000, 15000.0, False, True, False, 3) == int(base * (1.0 + S.SAM_SHARE + E.MD_SHARE + E.SA_SHARE))
-    assert S.expected_out_bytes(None, 1000, 15000.0, False, True, True, 1) == int(base * (1.0 + S.SAM_SHARE + S.BAM_SHARE + 2 * E.MD_SHARE))
-    assert S.expected_out_bytes(None, 1000, 15000.0, True, False, False, 3) == int(base * (1.0 + S.PAF_SHARE))
+    assert S.expected_out_bytes(None, 1000, 15000.0, S.TruthSpec(['sam'], 3)) == int(base * (1.0 + S.SAM_SHARE + E.MD_SHARE + E.SA_SHARE))
+    assert S.expected_out_bytes(None, 1000, 15000.0, S.TruthSpec(['sam', 'bam'], 1)) == int(base * (1.0 + S.SAM_SHARE + S.BAM_SHARE + 2 * E.MD_SHARE))
+    assert S.expected_out_bytes(None, 1000, 15000.0, S.TruthSpec(['paf'], 3)) == int(base * (1.0 + S.PAF_SHARE))
 
 
 def test_truth_tags_through_the_host_driver(tmp_path, monkeypatch):
