@@ -107,6 +107,11 @@ SIMULATE_OPTIONS = [
         ('--truth-eqx', dict(action='store_true', default=False, dest='truth_eqx',
                              help='Write the CIGARs of --truth-paf, --truth-sam and --truth-bam with = and X in place of M '
                                   '(such a PAF is not input for error_model / qscore_model)')),
+        ('--truth-depth', dict(type=str, default=None, dest='truth_depth', metavar='PATH',
+                               help='Also write the true coverage of the reference to PATH as bedGraph (plain text, no header): '
+                                    'contig, start, end (0-based, half-open) and the number of true alignments over every base, '
+                                    'zero-depth stretches included; works alone or with the other truth files; with '
+                                    '--output-shards every rank writes PATH.<rank>, the coverage by its own reads')),
         ('--gpu-streams', dict(type=int, default=None, dest='gpu_streams',
                                help='Device batches in flight per GPU, each on its own HIP stream (default: 6)')),
     ]),
@@ -212,7 +217,7 @@ def check_simulate_args(args):
     """Validate and derive the fields simulate() reads (mean_frag_length, identity triple, glitch_*)."""
     if not pathlib.Path(args.reference).is_file():
         sys.exit(f'Error: {args.reference} is not a file')
-    for flag in ('truth_paf', 'truth_sam', 'truth_bam'):
+    for flag in ('truth_paf', 'truth_sam', 'truth_bam', 'truth_depth'):
         path = getattr(args, flag, None)
         if path is not None and not pathlib.Path(path).resolve().parent.is_dir():
             sys.exit(f'Error: the directory of --{flag.replace("_", "-")} {path} does not exist')

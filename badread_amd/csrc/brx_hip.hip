@@ -14,6 +14,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -25,6 +26,7 @@
 #include "brx_paf.h"
 #include "brx_sam.h"
 #include "brx_bam.h"
+#include "brx_depth.h"
 
 #define BRX_KEV_MAX 2048
 
@@ -86,6 +88,7 @@ struct brx_ctx {
     const uint8_t *paf_frags;                                 /* MD:Z: -- the fragments (Fbuf: bottom of the arena, kept until the next batch) */
     uint8_t *h_sa, *d_sa; size_t sa_bytes;         /* pinned (mapped): SA:Z: -- one SaRec per record of the reads with two or more */
     uint8_t *h_paf, *d_paf; size_t paf_bytes;      /* pinned (mapped): per-read PAF bytes, primary records and offsets */
+    uint32_t depth_passes; float depth_ms[3];      /* the last brx_depth_bedgraph: its sort passes; ms of its sort, depth and text stages */
     char err[512];
 };
 
@@ -1274,7 +1277,7 @@ extern "C" int brx_bgzf_device(brx_ctx *c, const void *d_in, size_t n_bytes, voi
 }
 
 /* ---- truth alignments of the last simulate batch: PAF text (brx_paf.h), SAM records (brx_sam.h) or BAM records (brx_bam.h) ---- */
-enum { TRUTH_PAF = 0, TRUTH_SAM = 1, TRUTH_BAM = 2 };
+enum { TRUTH_PAF = 0, TRUTH_SAM = 1, TRUTH_BAM = 2, TRUTH_DEPTH = 3 };
 /* f(std::integral_constant<uint32_t, TAGS>, std::bool_constant<F>) for the tags and "some format bit" of a call: one instantiation of the SAM /
    BAM kernels per pair.  TAGS = 0 is the untagged code, nothing of the tags in its column loops; F = false the code of brx_emit_*_tags,
    nothing of the formats in it; with F the bits are a value of the grid's. */
@@ -1311,7 +1314,8 @@ static int emit_truth(brx_ctx *c, int kind, uint32_t fmt, uint32_t tags, uint32_
     uint32_t *len = (uint32_t *)(c->d_paf + len_at), *best = (uint32_t *)(c->d_paf + best_at), *n_rec = (uint32_t *)(c->d_paf + nrec_at);
     uint64_t *off = (uint64_t *)(c->d_paf + off_at), *rec_off = (uint64_t *)(c->d_paf + recoff_at);
     const uint8_t *arena = (const uint8_t *)c->scratch;
-    const bool sam = kind == TRUTH_SAM, bam = kind == TRUTH_BAM, sa = (tags & BRX_TAG_SA) != 0;
+    const bool sam = kind == TRUTH_SAM, bam = kind == TRUTH_BAM, depth = kind == TRUTH_DEPTH, sa = (tags & BRX_TAG_SA) != 0;
+    if (depth && ((uintptr_t)d_out & 7u)) return fail(c, BRX_E_ARG, "brx_emit_depth: the output buffer must be 8-byte aligned");
     const uint64_t *c_off = off, *c_rec_off = rec_off;
     const uint32_t *c_best = best;
     auto size = [&](auto T, auto F) {
@@ -1320,10 +1324,11 @@ static int emit_truth(brx_ctx *c, int kind, uint32_t fmt, uint32_t tags, uint32_
         else if (sam) hipLaunchKernelGGL((k_sam_size<TG, FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best, n_rec, fmt);
         else hipLaunchKernelGGL((k_paf_size<FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, fmt, len, best);
     };
-    if (n) with_tags_fmt(tags, fmt != 0, size);
+    if (n && depth) hipLaunchKernelGGL(k_depth_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len);
+    else if (n) with_tags_fmt(tags, fmt != 0, size);
     hipLaunchKernelGGL(k_truth_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
     if (sa) hipLaunchKernelGGL(k_truth_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)n_rec, rec_off);
-    { int rcw = wait_stream(c, st, bam ? "k_bam_size" : sam ? "k_sam_size" : "k_paf_size"); if (rcw) return rcw; }
+    { int rcw = wait_stream(c, st, depth ? "k_depth_size" : bam ? "k_bam_size" : sam ? "k_sam_size" : "k_paf_size"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
     const uint64_t total = ((const uint64_t *)(c->h_paf + off_at))[n];
     if (total > out_cap || (total && !d_out)) {
@@ -1351,9 +1356,10 @@ static int emit_truth(brx_ctx *c, int kind, uint32_t fmt, uint32_t tags, uint32_
         else hipLaunchKernelGGL((k_paf_write<FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, c->paf_seqbuf, c->paf_frags, fmt,
                                 c_off, c_best, d_out);
     };
-    if (n && total) with_tags_fmt(tags, fmt != 0, write);
+    if (n && total && depth) hipLaunchKernelGGL(k_depth_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, c_off, d_out);
+    else if (n && total) with_tags_fmt(tags, fmt != 0, write);
     if (d_read_off) HIPCHK(c, hipMemcpyAsync(d_read_off, c->h_paf + off_at, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-    { int rcw = wait_stream(c, st, bam ? "k_bam_write" : sam ? "k_sam_write" : "k_paf_write"); if (rcw) return rcw; }
+    { int rcw = wait_stream(c, st, depth ? "k_depth_write" : bam ? "k_bam_write" : sam ? "k_sam_write" : "k_paf_write"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
     *out_bytes = (size_t)total;
     return BRX_OK;
@@ -1387,4 +1393,137 @@ extern "C" int brx_emit_bam_tags(brx_ctx *c, uint32_t tags, uint32_t max_cigar_o
 }
 extern "C" int brx_emit_bam(brx_ctx *c, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
     return brx_emit_bam_fmt(c, 0, 0, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+}
+
+/* ---- the true coverage of the reference (brx_depth.h) ---- */
+extern "C" int brx_emit_depth(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
+    return emit_truth(c, TRUTH_DEPTH, 0, 0, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
+}
+
+/* where brx_depth_bedgraph keeps what in its scratch, for N keys (the events and four per contig) */
+struct DpPlan { uint64_t n; uint32_t n_tiles; size_t keys_a, keys_b, gk, gd, cd, table, incl, sums, flags, bytes; };
+static DpPlan dp_plan(uint64_t n) {
+    DpPlan p; p.n = n; p.n_tiles = (uint32_t)((n + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE);
+    const uint64_t cells = 256ull * p.n_tiles, longest = std::max(n, cells);
+    size_t at = 0;
+    auto take = [&](uint64_t bytes) { const size_t here = at; at += (size_t)((bytes + 255) & ~(uint64_t)255); return here; };
+    p.keys_a = take(n * 8); p.keys_b = take(n * 8); p.gk = take(n * 8); p.gd = take(n * 4); p.cd = take(n * 4);
+    p.table = take(cells * 4); p.incl = take(cells * 8);
+    p.sums = take(((longest + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE + 1) * 8); p.flags = take(256);
+    p.bytes = at + 256;                                  /* the caller's block may begin anywhere */
+    return p;
+}
+/* one inclusive scan: out[i] = the sum of src over [0, i] */
+template <class Src> static void dp_scan(hipStream_t st, Src src, uint64_t n, uint64_t *sums, uint64_t *out) {
+    const uint32_t nt = (uint32_t)((n + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE);
+    hipLaunchKernelGGL((k_dp_reduce<Src>), dim3(nt), dim3(BRX_DP_THREADS), 0, st, src, n, sums);
+    hipLaunchKernelGGL(k_dp_scan_sums, dim3(1), dim3(BRX_DP_THREADS), 0, st, sums, nt);
+    hipLaunchKernelGGL((k_dp_apply<Src>), dim3(nt), dim3(BRX_DP_THREADS), 0, st, src, n, (const uint64_t *)sums, out);
+}
+extern "C" size_t brx_depth_bedgraph_scratch(uint64_t n_events) { return dp_plan(n_events + 4ull * BRX_DEPTH_SCRATCH_CONTIGS).bytes; }
+extern "C" int brx_depth_last(const brx_ctx *c, uint32_t *sort_passes, float ms[3]) {
+    if (!c) return BRX_E_ARG;
+    if (sort_passes) *sort_passes = c->depth_passes;
+    if (ms) memcpy(ms, c->depth_ms, sizeof(c->depth_ms));
+    return BRX_OK;
+}
+static double dp_now_ms() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e3 + t.tv_nsec * 1e-6; }
+
+extern "C" int brx_depth_bedgraph(brx_ctx *c, const uint64_t *d_events, uint64_t n_events, uint8_t *d_out, size_t out_cap, size_t *out_bytes,
+                                  void *d_scratch, size_t scratch_bytes, void *hip_stream) {
+    if (!c || !out_bytes || (n_events && !d_events) || !d_scratch) return BRX_E_ARG;
+    *out_bytes = 0;
+    if (!c->has_ref) return fail(c, BRX_E_STATE, "brx_depth_bedgraph: reference not set");
+    const brx_reference &ref = c->dev.ref;
+    if (n_events & 1u) return fail(c, BRX_E_ARG, "brx_depth_bedgraph: %llu events: every record has two", (unsigned long long)n_events);
+    if (ref.n_contigs >= (1u << 24)) return fail(c, BRX_E_ARG, "brx_depth_bedgraph: %u contigs (an event holds fewer than 2^24)", ref.n_contigs);
+    const uint64_t n = n_events + 4ull * ref.n_contigs;
+    if (n >= (1ull << 31)) return fail(c, BRX_E_ARG, "brx_depth_bedgraph: %llu events and %u contigs: fewer than 2^31 keys in one call", (unsigned long long)n_events, ref.n_contigs);
+    const DpPlan P = dp_plan(n);
+    uint8_t *base = (uint8_t *)(((uintptr_t)d_scratch + 255) & ~(uintptr_t)255);
+    if (scratch_bytes < P.bytes) {
+        c->scratch_needed = P.bytes;
+        return fail(c, BRX_E_SCRATCH, "brx_depth_bedgraph: scratch too small (%zu < %zu)", scratch_bytes, P.bytes);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    uint64_t *keys[2] = { (uint64_t *)(base + P.keys_a), (uint64_t *)(base + P.keys_b) };
+    uint64_t *gk = (uint64_t *)(base + P.gk), *incl = (uint64_t *)(base + P.incl), *sums = (uint64_t *)(base + P.sums);
+    uint32_t *gd = (uint32_t *)(base + P.gd), *cd = (uint32_t *)(base + P.cd), *table = (uint32_t *)(base + P.table), *err = (uint32_t *)(base + P.flags);
+    const brx_contig *ct = ref.d_contigs;
+    const uint32_t nt = P.n_tiles;
+    double t0 = dp_now_ms();
+    /* the digits that can vary: the bytes of (the longest contig's length << 1 | 1) below bit 40, those of the last contig's index above */
+    uint32_t longest = 0;
+    {
+        std::vector<brx_contig> h(ref.n_contigs);
+        HIPCHK(c, hipMemcpyAsync(h.data(), ct, sizeof(brx_contig) * ref.n_contigs, hipMemcpyDeviceToHost, st));
+        { int rcw = wait_stream(c, st, "brx_depth_bedgraph (contigs)"); if (rcw) return rcw; }
+        for (const brx_contig &x : h) longest = std::max(longest, x.length);
+    }
+    uint32_t shifts[8], n_pass = 0;
+    for (uint32_t b = 0; b < 5; ++b) if (((((uint64_t)longest << 1) | 1u) >> (8 * b)) != 0) shifts[n_pass++] = 8 * b;
+    for (uint32_t b = 0; b < 3; ++b) if (((uint64_t)(ref.n_contigs - 1) >> (8 * b)) != 0) shifts[n_pass++] = 40 + 8 * b;
+    c->depth_passes = n_pass;
+    HIPCHK(c, hipMemsetAsync(err, 0, 256, st));
+    const DpSrcTable tab = { table };
+    for (uint32_t p = 0; p < n_pass; ++p) {
+        uint64_t *dst = keys[p & 1u];
+        if (p == 0) {
+            const DpKeysIn in = { d_events, n_events, ct };
+            hipLaunchKernelGGL((k_dp_hist<DpKeysIn, true>), dim3(nt), dim3(BRX_DP_THREADS), 0, st, in, n, shifts[p], nt, table, n_events, ct, ref.n_contigs, err);
+            dp_scan(st, tab, 256ull * nt, sums, incl);
+            hipLaunchKernelGGL((k_dp_scatter<DpKeysIn>), dim3(nt), dim3(BRX_DP_THREADS), 0, st, in, n, shifts[p], nt, (const uint32_t *)table, (const uint64_t *)incl, dst);
+        } else {
+            const DpKeysBuf in = { keys[(p - 1) & 1u] };
+            hipLaunchKernelGGL((k_dp_hist<DpKeysBuf, false>), dim3(nt), dim3(BRX_DP_THREADS), 0, st, in, n, shifts[p], nt, table, n_events, ct, ref.n_contigs, err);
+            dp_scan(st, tab, 256ull * nt, sums, incl);
+            hipLaunchKernelGGL((k_dp_scatter<DpKeysBuf>), dim3(nt), dim3(BRX_DP_THREADS), 0, st, in, n, shifts[p], nt, (const uint32_t *)table, (const uint64_t *)incl, dst);
+        }
+    }
+    uint64_t *sorted = keys[(n_pass - 1) & 1u], *spare = keys[n_pass & 1u];
+    uint32_t bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, err, 4, hipMemcpyDeviceToHost, st));
+    { int rcw = wait_stream(c, st, "brx_depth_bedgraph (sort)"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    if (bad) return fail(c, BRX_E_ARG, "brx_depth_bedgraph: an event names a contig outside the reference or a position beyond its contig");
+    double t1 = dp_now_ms();
+    c->depth_ms[0] = (float)(t1 - t0);
+    /* depth: from here on the keys are known to name contigs of the reference */
+    const DpSrcPack pack = { sorted, n };
+    dp_scan(st, pack, n, sums, spare);
+    hipLaunchKernelGGL(k_dp_groups, dim3((uint32_t)((n + BRX_DP_THREADS - 1) / BRX_DP_THREADS)), dim3(BRX_DP_THREADS), 0, st, (const uint64_t *)sorted, (const uint64_t *)spare, n, gk, gd, err);
+    uint64_t last = 0;
+    HIPCHK(c, hipMemcpyAsync(&last, spare + (n - 1), 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&bad, err, 4, hipMemcpyDeviceToHost, st));
+    { int rcw = wait_stream(c, st, "brx_depth_bedgraph (depth)"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    if (bad) return fail(c, BRX_E_ARG, "brx_depth_bedgraph: the events are not pairs of a start and a later end (depth below 0, or not 0 at a contig's end)");
+    const uint64_t n_groups = last >> 32;
+    const DpSrcChange change = { gk, gd, ct };
+    dp_scan(st, change, n_groups, sums, spare);
+    uint64_t *ck = sorted;                               /* the sorted keys have been read for the last time */
+    hipLaunchKernelGGL(k_dp_points, dim3((uint32_t)((n_groups + BRX_DP_THREADS - 1) / BRX_DP_THREADS)), dim3(BRX_DP_THREADS), 0, st, change, (const uint64_t *)spare, n_groups, ck, cd);
+    uint64_t n_points = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_points, spare + (n_groups - 1), 8, hipMemcpyDeviceToHost, st));
+    { int rcw = wait_stream(c, st, "brx_depth_bedgraph (change points)"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    double t2 = dp_now_ms();
+    c->depth_ms[1] = (float)(t2 - t1);
+    /* text */
+    const DpSrcLine line = { ck, cd, ct };
+    dp_scan(st, line, n_points, sums, spare);
+    uint64_t total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, spare + (n_points - 1), 8, hipMemcpyDeviceToHost, st));
+    { int rcw = wait_stream(c, st, "brx_depth_bedgraph (line sizes)"); if (rcw) return rcw; }
+    if (total > out_cap || (total && !d_out)) {
+        c->output_needed = (size_t)total;
+        return fail(c, BRX_E_OUTPUT, "brx_depth_bedgraph: output buffer too small: need %llu bytes", (unsigned long long)total);
+    }
+    hipLaunchKernelGGL(k_dp_lines, dim3((uint32_t)((n_points + BRX_DP_THREADS - 1) / BRX_DP_THREADS)), dim3(BRX_DP_THREADS), 0, st, line, (const uint64_t *)spare, n_points, ref.d_names, d_out);
+    { int rcw = wait_stream(c, st, "brx_depth_bedgraph (text)"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    c->depth_ms[2] = (float)(dp_now_ms() - t2);
+    *out_bytes = (size_t)total;
+    return BRX_OK;
 }

@@ -84,8 +84,12 @@ PAF_SHARE = 0.1
 SAM_SHARE = 1.5
 # --truth-bam: the same for a batch's BAM records before they are compressed (measured 1.14 on configs[3]: profiles/truth_bam.md)
 BAM_SHARE = 1.2
-TRUTH_KINDS = ('paf', 'sam', 'bam')      # the truth files, in the order a driver makes and ships them
-TRUTH_SHARE = dict(paf=PAF_SHARE, sam=SAM_SHARE, bam=BAM_SHARE)
+# --truth-depth: the same for a batch's events, 16 bytes per truth record (161 008-161 766 records per 1.97-1.98 GB of FASTQ on configs[3],
+# profiles/truth_paf.md: 8.2e-5 records per byte, so 0.0013; shipped with 15 % on top)
+DEPTH_SHARE = 0.0015
+TRUTH_KINDS = ('paf', 'sam', 'bam', 'depth')      # the truth files, in the order a driver makes and ships them
+TRUTH_SHARE = dict(paf=PAF_SHARE, sam=SAM_SHARE, bam=BAM_SHARE, depth=DEPTH_SHARE)
+DEPTH_TILE = 1024                      # include/brx.h: BRX_DEPTH_TILE, the events per workgroup of brx_depth_bedgraph's kernels
 # --truth-tags: what MD:Z: / SA:Z: add to a batch's SAM or BAM records, per FASTQ byte (measured 0.0574-0.0578 and 0.0097-0.0099 on
 # configs[3], the same within 0.0003 in BAM: profiles/truth_tags.md; MD grows with the error rate, and E_OUTPUT's retry is behind it)
 TAG_MD, TAG_SA = 1, 2                  # include/brx.h: BRX_TAG_MD, BRX_TAG_SA
@@ -324,6 +328,15 @@ def bind_library(lib):
                         ('brx_emit_paf_fmt', 1), ('brx_emit_sam_fmt', 2), ('brx_emit_bam_fmt', 3)):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [ctypes.c_void_p] + [ctypes.c_uint32] * words + emit_tail
+    lib.brx_emit_depth.restype = ctypes.c_int
+    lib.brx_emit_depth.argtypes = [ctypes.c_void_p] + emit_tail
+    lib.brx_depth_bedgraph_scratch.restype = ctypes.c_size_t
+    lib.brx_depth_bedgraph_scratch.argtypes = [ctypes.c_uint64]
+    lib.brx_depth_bedgraph.restype = ctypes.c_int
+    lib.brx_depth_bedgraph.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.brx_depth_last.restype = ctypes.c_int
+    lib.brx_depth_last.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_float * 3)]
     lib.brx_bgzf_device_bound.restype = ctypes.c_size_t
     lib.brx_bgzf_device_bound.argtypes = [ctypes.c_size_t]
     lib.brx_bgzf_device_scratch.restype = ctypes.c_size_t
@@ -577,7 +590,10 @@ class HipEngine(EngineBase):
         Returns (device uint8 tensor of the records in read order, numpy uint64 offsets of each read's records, n_reads + 1 entries).  The
         tensor is a fresh one: the engine may take its next batch at once.  The kinds may be asked for one batch in any order.
         `fmt`: FMT_EQX | FMT_CS | FMT_CS_LONG, =/X CIGAR runs and a cs:Z: behind AS.  `tags` (SAM, BAM): TAG_MD | TAG_SA adds MD:Z: / SA:Z:.
-        `max_cigar_ops` (BAM): a record with more CIGAR operations takes the CG:B:I form."""
+        `max_cigar_ops` (BAM): a record with more CIGAR operations takes the CG:B:I form.
+        'depth' (brx_emit_depth): the records' end points, two uint64 events per PAF record as bytes; tags and fmt take no part."""
+        if kind == 'depth':
+            return self._emit_truth(self.lib.brx_emit_depth, DEPTH_SHARE, n_reads)
         words = {'paf': (fmt,), 'sam': (fmt, tags), 'bam': (fmt, tags, max_cigar_ops)}[kind]
         entry = getattr(self.lib, f'brx_emit_{kind}_fmt')
         share = TRUTH_SHARE[kind] + (tag_share(tags) if kind != 'paf' else 0.0) + fmt_share(fmt, kind)
@@ -613,6 +629,37 @@ class HipEngine(EngineBase):
             cap = int(self.lib.brx_output_needed(self.ctx)) + 8
         self._check(rc)
         return out[:got.value]
+
+    def depth_bedgraph(self, events, cap=None):
+        """brx_depth_bedgraph: a tensor of events on this engine's device (int64 words, or their bytes as uint8: what emit_truth_device('depth')
+        returns, of any number of batches, in any order) -> a uint8 tensor (same device) with the bedGraph text of this engine's reference.
+        `cap`: the first output buffer (default 28 bytes per event + 64 KB: 26.6 measured on configs[3], profiles/truth_depth.md); E_OUTPUT
+        and E_SCRATCH cost one retry each."""
+        torch = self.torch
+        events = events.contiguous().view(torch.int64)
+        n = int(events.numel())
+        scratch_bytes = int(self.lib.brx_depth_bedgraph_scratch(n))
+        cap = int(cap) if cap is not None else 28 * n + (1 << 16)
+        got = ctypes.c_size_t(0)
+        for _ in range(3):
+            scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=self.device)
+            out = torch.zeros(max(cap, 8), dtype=torch.uint8, device=self.device)
+            rc = self.lib.brx_depth_bedgraph(self.ctx, ctypes.c_void_p(events.data_ptr()) if n else None, n, ctypes.c_void_p(out.data_ptr()), cap,
+                                             ctypes.byref(got), ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), self._stream())
+            if rc == E_OUTPUT:
+                cap = int(self.lib.brx_output_needed(self.ctx))
+            elif rc == E_SCRATCH:
+                scratch_bytes = int(self.lib.brx_scratch_needed(self.ctx))
+            else:
+                break
+        self._check(rc)
+        return out[:got.value]
+
+    def depth_last(self):
+        """(sort passes, {'sort': ms, 'depth': ms, 'text': ms}) of the last depth_bedgraph of this engine."""
+        passes, ms = ctypes.c_uint32(0), (ctypes.c_float * 3)()
+        self._check(self.lib.brx_depth_last(self.ctx, ctypes.byref(passes), ctypes.byref(ms)))
+        return int(passes.value), dict(zip(('sort', 'depth', 'text'), [float(x) for x in ms]))
 
     def _emit_truth(self, emit, share, n_reads):
         """brx_emit_paf / brx_emit_sam / brx_emit_bam into a buffer first sized as `share` of the expected FASTQ bytes; one retry on E_OUTPUT."""

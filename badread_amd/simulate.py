@@ -364,7 +364,9 @@ def kept_bytes(stats, first, base, last, n_mine):
 class TruthSpec(collections.namedtuple('TruthSpec', 'kinds tags fmt')):
     """What truth output a job writes beside its FASTQ: `kinds`, the files (--truth-paf, --truth-sam, --truth-bam) as a subset of
     ('paf', 'sam', 'bam') in that order, which is the order their records are made and shipped in; `tags` (--truth-tags), TAG_MD | TAG_SA
-    on the SAM and BAM records; `fmt` (--truth-eqx, --truth-cs), FMT_EQX | FMT_CS | FMT_CS_LONG on all three.  TruthSpec.NONE: none."""
+    on the SAM and BAM records; `fmt` (--truth-eqx, --truth-cs), FMT_EQX | FMT_CS | FMT_CS_LONG on all three.  'depth' (--truth-depth), the
+    last kind, is not a file of records: its batches are the records' end points, which its sink keeps until the job ends (_DepthFile);
+    tags and formats take no part in it.  TruthSpec.NONE: none."""
     __slots__ = ()
 
     def __new__(cls, kinds=(), tags=0, fmt=0):
@@ -380,8 +382,9 @@ class TruthSpec(collections.namedtuple('TruthSpec', 'kinds tags fmt')):
         """Bytes of truth records per FASTQ byte that a batch's buffers are first sized for: every file's own share, what the tags add to
         the SAM and the BAM records, what the formats add to each file."""
         share = sum(TRUTH_SHARE[k] for k in self.kinds)
-        share += tag_share(self.tags) * sum(k != 'paf' for k in self.kinds)
-        return share + sum(fmt_share(self.fmt, k) for k in self.kinds)
+        records = [k for k in self.kinds if k != 'depth']          # the files of records: the events of 'depth' carry neither tags nor formats
+        share += tag_share(self.tags) * sum(k != 'paf' for k in records)
+        return share + sum(fmt_share(self.fmt, k) for k in records)
 
 
 TruthSpec.NONE = TruthSpec()
@@ -1059,8 +1062,8 @@ class _PartsLog(object):
 class _Outputs(object):
     """Where a rank's bytes go (open_outputs): `write` to rank 0's stdout (through --gzip's sink if asked for); with --output-shards
     `local_write` and `local_parts`, this rank's own file and parts log (None where not in use); `truth_write`, {kind: the write of this
-    rank's --truth-<kind> file}."""
-    local_write = local_parts = None
+    rank's --truth-<kind> file}; `depth`, this rank's --truth-depth file (a _DepthFile, to be finished when the job has ended)."""
+    local_write = local_parts = depth = None
 
     def __init__(self, sink):
         self.sink, self.files, self.bam_files, self.truth_write = sink, [], [], {}
@@ -1155,7 +1158,68 @@ def open_outputs(args, shard, engine, stdout, pref=None):
             if header is not None:
                 f.write(header(first))
             outs.truth_write[kind] = f.write
+    # --truth-depth PATH: the coverage of the reference by the same records as bedGraph text.  The file's sink keeps the batches' events
+    # (16 bytes per record, the same ring and the same cut as the other truth files) and writes the file when the job has ended (_DepthFile);
+    # with --output-shards every rank writes PATH.<rank>, the coverage by the reads of its own FASTQ file
+    path = getattr(args, 'truth_depth', None)
+    if path:
+        if not hasattr(engine, 'depth_bedgraph'):
+            shard.finish()
+            sys.exit('Error: --truth-depth needs the GPU engine')
+        problem = depth_limits(pref)
+        if problem:                            # every rank alike: it depends on the reference alone
+            shard.finish()
+            sys.exit(f'Error: --truth-depth: {problem}')
+        if prefix or shard.rank == 0:
+            f = open(f'{path}.{shard.rank}' if prefix else path, 'wb')
+            outs.files.append(f)
+            zipped = gzip_level is not None or device_gzip
+            if zipped:
+                from .output import GzipSink
+            outs.depth = _DepthFile(GzipSink(f, gzip_level if gzip_level is not None else 6) if zipped else f)
+            outs.truth_write['depth'] = outs.depth.write
     return outs
+
+
+DEPTH_MAX_CONTIGS, DEPTH_MAX_LENGTH = 2 ** 24, 2 ** 39      # include/brx.h, BRX_DEPTH_EVENT: 24 bits of contig index, 39 of position
+
+
+def depth_limits(pref):
+    """Why --truth-depth cannot take this reference (None: it can): an event holds 24 bits of contig index and 39 of position."""
+    if len(pref.names) >= DEPTH_MAX_CONTIGS:
+        return f'{len(pref.names)} contigs, an event of brx_emit_depth holds fewer than 2^24'
+    long_ones = [str(n) for n, x in zip(pref.names, pref.lengths) if int(x) >= DEPTH_MAX_LENGTH]
+    if long_ones:
+        return f'contig {long_ones[0]} has 2^39 or more bases, more than an event of brx_emit_depth holds'
+    return None
+
+
+class _DepthFile(object):
+    """The sink of --truth-depth.  `write` (the ring's writer thread) keeps the events of every batch: those of the reads the FASTQ holds,
+    cut where the FASTQ is cut, of every rank on rank 0 or with --output-shards this rank's own.  `finish`, called once when the job has
+    ended normally, uploads them, has the engine -- still open, its batches done -- make the text (brx_depth_bedgraph) and writes it.
+    Events and scratch must fit the device then; a job that does not reach `finish` writes nothing."""
+
+    def __init__(self, sink):
+        self.sink, self.parts = sink, []
+
+    def write(self, part):
+        self.parts.append(bytes(part))          # the ring's buffer is reused
+
+    def finish(self, engine):
+        torch = engine.torch
+        events = np.frombuffer(b''.join(self.parts), dtype='<i8')
+        self.parts = []
+        need = events.nbytes + int(engine.lib.brx_depth_bedgraph_scratch(len(events)))
+        try:
+            if getattr(engine.device, 'type', 'cpu') == 'cuda':
+                torch.cuda.empty_cache()        # the batches' buffers, back to the driver
+                if need + 28 * len(events) > torch.cuda.mem_get_info(engine.device)[0]:
+                    raise MemoryError
+            text = engine.depth_bedgraph(torch.from_numpy(events.copy()).to(engine.device))
+        except (MemoryError, getattr(torch, 'OutOfMemoryError', MemoryError)):
+            sys.exit(f'Error: --truth-depth: {len(events) // 2} records need {need / 1e9:.1f} GB on the device')
+        self.sink.write(memoryview(text.cpu().numpy()))
 
 
 def sam_header(pref):
@@ -1230,6 +1294,8 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
                                  in_flight=getattr(args, 'gpu_streams', None) or DEFAULT_IN_FLIGHT, device_gzip=bool(getattr(args, 'gzip_device', False)),
                                  local_write=outs.local_write, local_parts=outs.local_parts, expected_error=expected_error_rate(identities),
                                  arenas=arenas, truth=truth, truth_write=outs.truth_write)
+            if outs.depth is not None:      # the job has ended normally: the coverage of the events it kept, on the engine that is still open
+                outs.depth.finish(engine)
         finally:
             outs.close()
     except (SystemExit, OSError):

@@ -413,6 +413,38 @@ int brx_emit_sam_fmt(brx_ctx *ctx, uint32_t fmt, uint32_t tags, uint8_t *d_out, 
 int brx_emit_bam_fmt(brx_ctx *ctx, uint32_t fmt, uint32_t tags, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off,
                      size_t *out_bytes, void *hip_stream);
 
+/* ---- the true coverage of the reference (README: --truth-depth) ----
+ * brx_emit_depth: the end points of the truth records of the LAST brx_simulate_batch on ctx, a fourth truth kind under brx_emit_paf's
+ * contract: BRX_E_STATE where there is no batch, BRX_E_OUTPUT + brx_output_needed() with nothing written, d_read_off in bytes,
+ * synchronous, stateless, callable in any order with the other emitters, which stay byte-identical.  Its "records" are events: two
+ * little-endian uint64 per PAF record, in PAF order, the start event and then the end event (d_out 8-byte aligned):
+ *   event = contig index << 40 | position << 1 | is_start       start: position = tstart, is_start = 1; end: position = tend, is_start = 0
+ * so a reference may have up to 2^24 - 1 contigs of fewer than 2^39 bases. */
+#define BRX_DEPTH_EVENT(contig, position, is_start) (((uint64_t)(contig) << 40) | ((uint64_t)(position) << 1) | (uint64_t)(is_start))
+int brx_emit_depth(brx_ctx *ctx, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream);
+
+/* brx_depth_bedgraph: n_events events (device memory, any order, from any number of batches) against the reference of ctx
+ * (brx_set_reference) -> the bedGraph text of the whole reference in d_out: `contig TAB start TAB end TAB depth LF`, 0-based half-open,
+ * no header.  depth(contig, p) = the events' records with tstart <= p < tend.  Every contig is covered from 0 to its length, in
+ * reference order, by maximal runs of equal depth, zero-depth runs included; a contig without a record is one line.  The bytes are the
+ * same for every permutation of the events; n_events = 0 gives one zero line per contig.
+ *   BRX_E_OUTPUT + brx_output_needed()   out_cap is too small; nothing written.
+ *   BRX_E_ARG, nothing written           n_events is odd; an event names a contig outside the reference or a position beyond its contig's
+ *                                        length; the running depth is negative somewhere or not zero at a contig's end; 2^24 or more
+ *                                        contigs; 2^31 or more keys (n_events + 4 per contig).
+ *   BRX_E_SCRATCH + brx_scratch_needed() d_scratch is too small: brx_depth_bedgraph_scratch(n_events) is enough for a reference of up to
+ *                                        BRX_DEPTH_SCRATCH_CONTIGS contigs, each further contig takes four more events' worth.
+ *   BRX_E_STATE                          no reference.
+ * The events are sorted (LSD radix sort, 8 bits per pass, only the digits that the contig count and the longest contig let vary), summed
+ * (+1 / -1 from the low bit) and written by workgroups of 256 threads over tiles of BRX_DEPTH_TILE keys.  Synchronous on `hip_stream`.
+ * brx_depth_last: the sort passes of the last call on ctx and the host-side ms of its three stages (sort, depth, text). */
+#define BRX_DEPTH_TILE 1024u
+#define BRX_DEPTH_SCRATCH_CONTIGS 4096u
+size_t brx_depth_bedgraph_scratch(uint64_t n_events);
+int brx_depth_bedgraph(brx_ctx *ctx, const uint64_t *d_events, uint64_t n_events, uint8_t *d_out, size_t out_cap, size_t *out_bytes,
+                       void *d_scratch, size_t scratch_bytes, void *hip_stream);
+int brx_depth_last(const brx_ctx *ctx, uint32_t *sort_passes, float ms[3]);
+
 /* n_bytes of device memory as BGZF blocks (SAM spec v1 section 4.1) back to back, one per BRX_BGZF_BLOCK input bytes, the last
  * one possibly shorter, none for no input: the members of brx_gzip_device (one dynamic Huffman code per block, no match search)
  * behind the 18-byte BGZF header (FEXTRA, 'B' 'C', BSIZE = the block's size - 1).  A block needs at most 61 607 bytes, so every
