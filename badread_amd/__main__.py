@@ -1,11 +1,11 @@
 """
-`badread simulate` command line for the MI355X path (python -m badread_amd simulate ...).
+The `badread` command line for the MI355X path (python -m badread_amd simulate | error_model | qscore_model | plot ...).
 
 Flags, defaults, derived fields, validation messages and exit codes follow the reference CLI
 (/root/reference/badread/__main__.py:83-147 flags, :239-336 checks) so that existing command lines and
 scripts keep working.  `error_model` and `qscore_model` (the model builders) run their counting
-loops on the GPU (badread_amd/model_builder.py); `plot` is outside this build's scope and refused with a message.  Additive options:
---gpu-batch (reads per device batch).  Multi-GPU: launch with
+loops on the GPU (badread_amd/model_builder.py), and so does `plot` with its per-base and per-window loops
+(badread_amd/plot_window_identity.py; only drawing needs matplotlib).  Additive options: the MI355X group of each command.  Multi-GPU: launch with
 `python -m torch.distributed.run --nproc-per-node N -m badread_amd simulate ...`; rank 0 writes stdout.
 """
 import argparse
@@ -24,7 +24,7 @@ from .version import __version__
 
 ERROR_MODEL_NAMES = ['random', 'nanopore2018', 'nanopore2020', 'nanopore2023', 'pacbio2016', 'pacbio2021']
 QSCORE_MODEL_NAMES = ['random', 'ideal', 'nanopore2018', 'nanopore2020', 'nanopore2023', 'pacbio2016', 'pacbio2021']
-OUT_OF_SCOPE = ('plot',)
+OUT_OF_SCOPE = ()                        # commands of the reference that are parsed and then refused: none is left
 
 # (group title, group description, [(flag, kwargs), ...]) -- help texts as in the reference
 SIMULATE_OPTIONS = [
@@ -168,6 +168,24 @@ def parse_args(argv):
     opt.add_argument('--max_output', type=int, default=10000, help='The outputted model will be limited to this many lines')
     _add_help_group(em)
     _add_help_group(qm)
+    # plot: flags and defaults of the reference (__main__.py:208-228) and a group of additive ones
+    pl = subparsers.add_parser('plot', description='View read identities over a sliding window', add_help=False)
+    req = pl.add_argument_group('Required arguments')
+    req.add_argument('--reference', type=str, required=True, help='Reference FASTA file')
+    req.add_argument('--reads', type=str, required=True, help='FASTQ of real reads')
+    req.add_argument('--alignment', type=str, required=True, help='PAF alignment of reads aligned to reference')
+    opt = pl.add_argument_group('Optional arguments')
+    opt.add_argument('--window', type=int, default=100, help='Window size in bp')
+    opt.add_argument('--qual', action='store_true', help='Include qscores in plot (default: only show identity)')
+    opt.add_argument('--no_plot', action='store_true', help='Do not display plots (for testing purposes)')
+    gpu = pl.add_argument_group('MI355X', description='Additive options (no effect on the numbers)')
+    gpu.add_argument('--summary', type=str, default=None, metavar='PATH',
+                     help='Write one TSV line per alignment to PATH: the alignment, its number of windows, the lowest window '
+                          'identity and where it is, the highest and the mean (with --qual the same of the window qualities)')
+    gpu.add_argument('--save', type=str, default=None, metavar='DIR',
+                     help='Save one PNG per alignment to DIR/<index>_<read name>.png instead of displaying it')
+    gpu.add_argument('--max_alignments', type=int, help='Only use this many alignments of the PAF (default: use all alignments)')
+    _add_help_group(pl)
     for name in OUT_OF_SCOPE:
         sub = subparsers.add_parser(name, add_help=False, description=f'{name}: not part of the MI355X build')
         sub.add_argument('rest', nargs=argparse.REMAINDER)
@@ -316,6 +334,9 @@ def main(output=sys.stderr):
     elif args.subparser_name == 'qscore_model':
         from .model_builder import make_qscore_model
         make_qscore_model(args, output=output)
+    elif args.subparser_name == 'plot':
+        from .plot_window_identity import plot_window_identity
+        plot_window_identity(args)
     elif args.subparser_name in OUT_OF_SCOPE:
         sys.exit(f'Error: the {args.subparser_name} command is not part of the MI355X simulate build; '
                  f'use the reference Badread for it')

@@ -27,6 +27,7 @@
 #include "brx_sam.h"
 #include "brx_bam.h"
 #include "brx_depth.h"
+#include "brx_window.h"
 
 #define BRX_KEV_MAX 2048
 
@@ -89,6 +90,7 @@ struct brx_ctx {
     uint8_t *h_sa, *d_sa; size_t sa_bytes;         /* pinned (mapped): SA:Z: -- one SaRec per record of the reads with two or more */
     uint8_t *h_paf, *d_paf; size_t paf_bytes;      /* pinned (mapped): per-read PAF bytes, primary records and offsets */
     uint32_t depth_passes; float depth_ms[3];      /* the last brx_depth_bedgraph: its sort passes; ms of its sort, depth and text stages */
+    float window_ms[4];                            /* the last brx_window_means under brx_set_kernel_timing: errors, scans, statistics, values */
     char err[512];
 };
 
@@ -1525,5 +1527,64 @@ extern "C" int brx_depth_bedgraph(brx_ctx *c, const uint64_t *d_events, uint64_t
     HIPCHK(c, hipGetLastError());
     c->depth_ms[2] = (float)(dp_now_ms() - t2);
     *out_bytes = (size_t)total;
+    return BRX_OK;
+}
+
+/* ---- window identities (brx_window.h) ---- */
+struct PwPlan { uint32_t n_tiles; size_t err, pe, pq, sums, bytes; };
+static PwPlan pw_plan(uint64_t n_bases, int want_qual) {
+    PwPlan p; p.n_tiles = (uint32_t)((n_bases + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE);
+    size_t at = 0;
+    auto take = [&](uint64_t bytes) { const size_t here = at; at += (size_t)((bytes + 255) & ~(uint64_t)255); return here; };
+    p.err = take(n_bases * 4); p.pe = take((n_bases + 1) * 8); p.pq = take(want_qual ? (n_bases + 1) * 8 : 0);
+    p.sums = take(((uint64_t)p.n_tiles + 1) * 8);
+    p.bytes = at + 256;                                  /* the caller's block may begin anywhere */
+    return p;
+}
+extern "C" size_t brx_window_scratch(uint64_t n_bases, int want_qual) { return pw_plan(n_bases, want_qual).bytes; }
+extern "C" int brx_window_last(const brx_ctx *c, float ms[4]) {
+    if (!c || !ms) return BRX_E_ARG;
+    memcpy(ms, c->window_ms, sizeof(c->window_ms));
+    return BRX_OK;
+}
+extern "C" int brx_window_means(brx_ctx *c, const brx_window_job *job, void *hip_stream) {
+    if (!c || !job) return BRX_E_ARG;
+    const brx_window_job j = *job;
+    if (j.window == 0) return fail(c, BRX_E_ARG, "brx_window_means: window 0");
+    if (j.n_align == 0) return BRX_OK;
+    if (!j.d_align_read_off || !j.d_align_part_off || !j.d_align_win_off || !j.d_stat) return fail(c, BRX_E_ARG, "brx_window_means: an offset array or d_stat is NULL");
+    if (j.n_bases && (!j.d_seq || !j.d_ref || !j.d_part_type || !j.d_part_len || !j.d_part_read || !j.d_part_ref || (j.want_qual && !j.d_qual)))
+        return fail(c, BRX_E_ARG, "brx_window_means: a slice or part array is NULL");
+    if (j.n_bases >= (1ull << 39)) return fail(c, BRX_E_ARG, "brx_window_means: %llu read bases: fewer than 2^39 in one call", (unsigned long long)j.n_bases);
+    if (j.n_windows > j.n_bases) return fail(c, BRX_E_ARG, "brx_window_means: more windows than read bases");
+    const PwPlan P = pw_plan(j.n_bases, (int)j.want_qual);
+    if (!j.d_scratch || j.scratch_bytes < P.bytes) {
+        c->scratch_needed = P.bytes;
+        return fail(c, BRX_E_SCRATCH, "brx_window_means: scratch too small (%zu < %zu)", j.scratch_bytes, P.bytes);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    uint8_t *base = (uint8_t *)(((uintptr_t)j.d_scratch + 255) & ~(uintptr_t)255);
+    uint32_t *err = (uint32_t *)(base + P.err);
+    uint64_t *pe = (uint64_t *)(base + P.pe), *pq = j.want_qual ? (uint64_t *)(base + P.pq) : nullptr, *sums = (uint64_t *)(base + P.sums);
+    const bool timed = c->ktiming && c->kev_b[0];            /* the event pool of brx_set_kernel_timing: five marks */
+    auto mark = [&](int i) { if (timed) (void)hipEventRecord(c->kev_b[i], st); };
+    mark(0);
+    if (j.n_bases) {
+        hipLaunchKernelGGL(k_pw_errors, dim3((uint32_t)((j.n_bases + BRX_PW_THREADS - 1) / BRX_PW_THREADS)), dim3(BRX_PW_THREADS), 0, st, j, err, pe, pq);
+        mark(1);
+        const DpSrcTable e = { err };
+        dp_scan(st, e, j.n_bases, sums, pe + 1);
+        if (pq) { const PwSrcQual q = { j.d_qual }; dp_scan(st, q, j.n_bases, sums, pq + 1); }
+    } else mark(1);
+    mark(2);
+    hipLaunchKernelGGL(k_pw_stats, dim3(j.n_align), dim3(BRX_PW_THREADS), 0, st, j, (const uint64_t *)pe, (const uint64_t *)pq);
+    mark(3);
+    if (j.n_windows && (j.d_err_sum || j.d_qual_sum))
+        hipLaunchKernelGGL(k_pw_values, dim3((uint32_t)((j.n_windows + BRX_PW_THREADS - 1) / BRX_PW_THREADS)), dim3(BRX_PW_THREADS), 0, st, j, (const uint64_t *)pe, (const uint64_t *)pq);
+    mark(4);
+    { int rcw = wait_stream(c, st, "brx_window_means"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    if (timed) for (int i = 0; i < 4; ++i) HIPCHK(c, hipEventElapsedTime(&c->window_ms[i], c->kev_b[i], c->kev_b[i + 1]));
     return BRX_OK;
 }

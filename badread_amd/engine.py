@@ -135,6 +135,24 @@ class BrxModelJob(ctypes.Structure):
                 ('d_spill', ctypes.c_void_p), ('spill_cap', ctypes.c_uint32)]
 
 
+class BrxWindowJob(ctypes.Structure):
+    """brx_window_job of include/brx.h"""
+    _fields_ = [('n_align', ctypes.c_uint32), ('window', ctypes.c_uint32), ('want_qual', ctypes.c_uint32), ('reserved', ctypes.c_uint32),
+                ('n_bases', ctypes.c_uint64), ('n_windows', ctypes.c_uint64),
+                ('d_seq', ctypes.c_void_p), ('d_qual', ctypes.c_void_p), ('d_ref', ctypes.c_void_p),
+                ('d_part_type', ctypes.c_void_p), ('d_part_len', ctypes.c_void_p),
+                ('d_part_read', ctypes.c_void_p), ('d_part_ref', ctypes.c_void_p),
+                ('d_align_part_off', ctypes.c_void_p), ('d_align_read_off', ctypes.c_void_p), ('d_align_win_off', ctypes.c_void_p),
+                ('d_stat', ctypes.c_void_p), ('d_err_sum', ctypes.c_void_p), ('d_qual_sum', ctypes.c_void_p),
+                ('d_scratch', ctypes.c_void_p), ('scratch_bytes', ctypes.c_size_t)]
+
+
+# brx_window_stat of include/brx.h
+WINDOW_STAT_DTYPE = np.dtype([('n', '<u4'), ('err_min', '<u4'), ('err_max', '<u4'), ('err_argmax', '<u4'), ('err_total', '<u8'),
+                              ('qual_min', '<i4'), ('qual_max', '<i4'), ('qual_total', '<i8')])
+assert WINDOW_STAT_DTYPE.itemsize == 40
+
+
 class BrxKernelStat(ctypes.Structure):
     _fields_ = [('launches', ctypes.c_uint32), ('ms', ctypes.c_float), ('bases', ctypes.c_double)]
 
@@ -337,6 +355,12 @@ def bind_library(lib):
                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     lib.brx_depth_last.restype = ctypes.c_int
     lib.brx_depth_last.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_float * 3)]
+    lib.brx_window_scratch.restype = ctypes.c_size_t
+    lib.brx_window_scratch.argtypes = [ctypes.c_uint64, ctypes.c_int]
+    lib.brx_window_means.restype = ctypes.c_int
+    lib.brx_window_means.argtypes = [ctypes.c_void_p, ctypes.POINTER(BrxWindowJob), ctypes.c_void_p]
+    lib.brx_window_last.restype = ctypes.c_int
+    lib.brx_window_last.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float * 4)]
     lib.brx_bgzf_device_bound.restype = ctypes.c_size_t
     lib.brx_bgzf_device_bound.argtypes = [ctypes.c_size_t]
     lib.brx_bgzf_device_scratch.restype = ctypes.c_size_t
@@ -784,6 +808,48 @@ class HipEngine(EngineBase):
         used = h_keys != np.uint64(0xFFFFFFFFFFFFFFFF)
         return (h_keys[used], counts.cpu().numpy()[used].astype(np.int64), first.cpu().numpy().view(np.uint64)[used],
                 spill[:n_spill].cpu().numpy().view(np.uint64))
+
+    def window_means(self, job, window, qual, values=False):
+        """brx_window_means over a model_builder.Job: (stats, err_sum, qual_sum).  stats: one WINDOW_STAT_DTYPE record per alignment;
+        err_sum / qual_sum: the window sums of all alignments back to back (uint32 / int32; an alignment's begin at the prefix sums
+        of stats['n']), None unless `values`, qual_sum None without `qual`.  The doubles of the reference are made from these
+        integers by the caller (plot_window_identity.py)."""
+        torch = self.torch
+        keep = []
+
+        def up(arr):
+            ptr, t = self._upload(arr)
+            keep.append(t)
+            return ptr
+        dev = self.device
+        lengths = np.diff(job.align_read_off.astype(np.int64))
+        n_win = np.maximum(lengths - int(window), 0)
+        win_off = np.concatenate(([0], np.cumsum(n_win))).astype(np.uint64)
+        n_bases, n_windows = int(job.align_read_off[-1]), int(win_off[-1])
+        stats = torch.zeros(max(job.n_align, 1) * WINDOW_STAT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        err_sum = torch.empty(max(n_windows, 1), dtype=torch.int32, device=dev) if values else None
+        qual_sum = torch.empty(max(n_windows, 1), dtype=torch.int32, device=dev) if values and qual else None
+        scratch = torch.empty(int(self.lib.brx_window_scratch(n_bases, int(bool(qual)))), dtype=torch.uint8, device=dev)
+        s = BrxWindowJob()
+        s.n_align, s.window, s.want_qual, s.n_bases, s.n_windows = job.n_align, int(window), int(bool(qual)), n_bases, n_windows
+        s.d_seq, s.d_qual, s.d_ref = up(job.seq), up(job.qual), up(job.ref)
+        s.d_part_type, s.d_part_len = up(job.part_type), up(job.part_len)
+        s.d_part_read, s.d_part_ref = up(job.part_read), up(job.part_ref)
+        s.d_align_part_off, s.d_align_read_off, s.d_align_win_off = up(job.align_part_off), up(job.align_read_off), up(win_off)
+        s.d_stat = stats.data_ptr()
+        s.d_err_sum = err_sum.data_ptr() if err_sum is not None else None
+        s.d_qual_sum = qual_sum.data_ptr() if qual_sum is not None else None
+        s.d_scratch, s.scratch_bytes = scratch.data_ptr(), scratch.numel()
+        self._check(self.lib.brx_window_means(self.ctx, ctypes.byref(s), self._stream()))
+        h_stats = np.frombuffer(stats.cpu().numpy().tobytes(), dtype=WINDOW_STAT_DTYPE)[:job.n_align]
+        return (h_stats, err_sum[:n_windows].cpu().numpy().view(np.uint32) if err_sum is not None else None,
+                qual_sum[:n_windows].cpu().numpy() if qual_sum is not None else None)
+
+    def window_last(self):
+        """ms of the kernels of the last window_means under set_kernel_timing: errors, scans, stats, values."""
+        ms = (ctypes.c_float * 4)()
+        self._check(self.lib.brx_window_last(self.ctx, ctypes.byref(ms)))
+        return dict(zip(('errors', 'scans', 'stats', 'values'), [float(x) for x in ms]))
 
     def gzip_device(self, data, block_off=None):
         """brx_gzip_device: a uint8 tensor of FASTQ text on this engine's device -> a uint8 tensor (same device) holding

@@ -38,7 +38,7 @@ class Job(object):
     def __init__(self, refs, reads, alignments):
         seqs, quals, refsl = [], [], []
         ptype, plen, pcol, pread, pref = [], [], [], [], []
-        a_part, a_col = [0], [0]
+        a_part, a_col, a_read = [0], [0], [0]
         col = rpos = fpos = 0
         self.slices = []
         for a in alignments:
@@ -62,7 +62,7 @@ class Job(object):
                     fpos += n
             rpos, fpos = r0 + len(read_seq), f0 + len(ref_seq)
             seqs.append(read_seq); quals.append(read_qual[:len(read_seq)]); refsl.append(ref_seq)
-            a_part.append(len(ptype)); a_col.append(col)
+            a_part.append(len(ptype)); a_col.append(col); a_read.append(rpos)
             self.slices.append((read_seq, read_qual, ref_seq, parts))
         enc = lambda parts_: np.frombuffer(''.join(parts_).encode('latin-1') or b'\0', dtype=np.uint8)
         self.seq, self.qual, self.ref = enc(seqs), enc(quals), enc(refsl)
@@ -71,6 +71,7 @@ class Job(object):
         self.part_col, self.part_read, self.part_ref = (np.array(x or [0], dtype=np.uint64) for x in (pcol, pread, pref))
         self.align_part_off = np.array(a_part, dtype=np.uint64)
         self.align_col_off = np.array(a_col, dtype=np.uint64)
+        self.align_read_off = np.array(a_read, dtype=np.uint64)      # where each alignment's read slice begins in seq / qual
         self.n_align, self.n_cols = len(alignments), col
 
     def gapped(self, a, gap):

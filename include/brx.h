@@ -336,6 +336,48 @@ typedef struct {
 } brx_model_job;
 int brx_model_count(brx_ctx *ctx, int kind, const brx_model_job *job, void *hip_stream);
 
+/* ------------------------------------------------------------------ window identities (README: Window identities (`plot`))
+ * The numbers of `badread plot` (align_sequences' errors_per_read_pos, alignment.py:103-132, and get_window_means,
+ * plot_window_identity.py:54-70) over a set of alignments, all of them integers; the host makes the reference's doubles from them.
+ * Input: the arrays of brx_model_job that hold the slices and the CIGAR parts (device memory; the column offsets are not needed),
+ * d_align_read_off (n_align + 1: where each alignment's read slice begins in d_seq / d_qual, the last entry = n_bases), `window`
+ * (W >= 1) and d_align_win_off (n_align + 1: the prefix sums of n, the last entry = n_windows).  For alignment a with a read slice
+ * of L bases:
+ *   E[p]  errors of read base p: an M column counts 1 where read and reference bytes differ, an I column 1, a D part its length at
+ *         the read base behind it (the first base behind the CIGAR for a trailing one); bases the CIGAR does not reach count 0
+ *   n     max(L - W, 0) windows -- not L - W + 1: the reference leaves the last one out
+ *   S[i]  E[i] + .. + E[i + W - 1], 0 <= i < n;   Q[i] the same sum over q = quality byte - 33 (signed), when want_qual
+ * Output: d_stat[a] = n, the smallest and largest S, the smallest i with the largest S, the sum of the S, and the same of Q without
+ * the argmax (0 without want_qual); min, max and argmax are 0 where n = 0.  d_err_sum / d_qual_sum (either may be NULL): S[i] and
+ * Q[i] at d_align_win_off[a] + i.  The caller keeps every alignment below 2^31 columns (and 223 L below 2^31 with want_qual), so the
+ * 32-bit sums are exact.  d_scratch: brx_window_scratch(n_bases, want_qual) bytes of device memory.  Zero alignments, zero windows
+ * and a window longer than every read are valid calls.  No atomics and no waiting between workgroups: the results do not depend on
+ * scheduling.  Synchronous on `hip_stream`.
+ *   BRX_E_ARG                             window 0, a NULL array that is needed, n_bases of 2^39 or more
+ *   BRX_E_SCRATCH + brx_scratch_needed()  scratch_bytes is too small; nothing written.                                            */
+typedef struct {
+    uint32_t n, err_min, err_max, err_argmax;
+    uint64_t err_total;
+    int32_t qual_min, qual_max;
+    int64_t qual_total;
+} brx_window_stat;
+typedef struct {
+    uint32_t n_align, window, want_qual, reserved;
+    uint64_t n_bases, n_windows;
+    const uint8_t *d_seq, *d_qual, *d_ref;
+    const uint8_t *d_part_type;
+    const uint32_t *d_part_len;
+    const uint64_t *d_part_read, *d_part_ref;
+    const uint64_t *d_align_part_off, *d_align_read_off, *d_align_win_off;
+    brx_window_stat *d_stat;
+    uint32_t *d_err_sum; int32_t *d_qual_sum;
+    void *d_scratch; size_t scratch_bytes;
+} brx_window_job;
+size_t brx_window_scratch(uint64_t n_bases, int want_qual);
+int brx_window_means(brx_ctx *ctx, const brx_window_job *job, void *hip_stream);
+/* ms between HIP events of the last brx_window_means on ctx that ran under brx_set_kernel_timing: errors, the scans, statistics, values */
+int brx_window_last(const brx_ctx *ctx, float ms[4]);
+
 /* ---- output stage: the FASTQ bytes of a batch as gzip members, made on the device ----
  * Replaces the `| gzip` the reference's users put behind /root/reference/badread/simulate.py:73-82 (print of the
  * record text).  d_in: n_bytes of text in device memory.  d_block_off: n_blocks + 1 ascending byte offsets (device
