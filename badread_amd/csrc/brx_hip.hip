@@ -28,6 +28,7 @@
 #include "brx_bam.h"
 #include "brx_depth.h"
 #include "brx_window.h"
+#include "brx_pafin.h"
 
 #define BRX_KEV_MAX 2048
 
@@ -91,6 +92,7 @@ struct brx_ctx {
     uint8_t *h_paf, *d_paf; size_t paf_bytes;      /* pinned (mapped): per-read PAF bytes, primary records and offsets */
     uint32_t depth_passes; float depth_ms[3];      /* the last brx_depth_bedgraph: its sort passes; ms of its sort, depth and text stages */
     float window_ms[4];                            /* the last brx_window_means under brx_set_kernel_timing: errors, scans, statistics, values */
+    float loader_ms[2];                            /* the last brx_paf_scan and brx_align_pack under brx_set_kernel_timing */
     char err[512];
 };
 
@@ -1586,5 +1588,90 @@ extern "C" int brx_window_means(brx_ctx *c, const brx_window_job *job, void *hip
     { int rcw = wait_stream(c, st, "brx_window_means"); if (rcw) return rcw; }
     HIPCHK(c, hipGetLastError());
     if (timed) for (int i = 0; i < 4; ++i) HIPCHK(c, hipEventElapsedTime(&c->window_ms[i], c->kev_b[i], c->kev_b[i + 1]));
+    return BRX_OK;
+}
+
+/* ---- the device loader (brx_pafin.h) ---- */
+struct PiPlan { uint32_t n_tiles; size_t incl, sums, flags, bytes; };
+static PiPlan pi_plan(uint64_t n_bytes) {
+    PiPlan p; p.n_tiles = (uint32_t)((n_bytes + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE);
+    size_t at = 0;
+    auto take = [&](uint64_t bytes) { const size_t here = at; at += (size_t)((bytes + 255) & ~(uint64_t)255); return here; };
+    p.incl = take(n_bytes * 8); p.sums = take(((uint64_t)p.n_tiles + 1) * 8); p.flags = take(256);
+    p.bytes = at + 256;                                  /* the caller's block may begin anywhere */
+    return p;
+}
+extern "C" size_t brx_paf_scan_scratch(uint64_t n_bytes) { return pi_plan(n_bytes).bytes; }
+extern "C" int brx_loader_last(const brx_ctx *c, float ms[2]) {
+    if (!c || !ms) return BRX_E_ARG;
+    memcpy(ms, c->loader_ms, sizeof(c->loader_ms));
+    return BRX_OK;
+}
+extern "C" int brx_paf_scan(brx_ctx *c, const uint8_t *d_text, uint64_t n_bytes, uint64_t max_lines, brx_paf_line *d_lines, uint64_t line_cap,
+                            uint64_t *n_lines, void *d_scratch, size_t scratch_bytes, void *hip_stream) {
+    if (!c) return BRX_E_ARG;
+    if (!n_lines) return fail(c, BRX_E_ARG, "brx_paf_scan: n_lines is NULL");
+    *n_lines = 0;
+    if (n_bytes == 0) return BRX_OK;
+    if (!d_text) return fail(c, BRX_E_ARG, "brx_paf_scan: d_text is NULL");
+    if (n_bytes >= (1ull << 42)) return fail(c, BRX_E_ARG, "brx_paf_scan: %llu bytes: fewer than 2^42 in one call", (unsigned long long)n_bytes);
+    const PiPlan P = pi_plan(n_bytes);
+    if (!d_scratch || scratch_bytes < P.bytes) {
+        c->scratch_needed = P.bytes;
+        return fail(c, BRX_E_SCRATCH, "brx_paf_scan: scratch too small (%zu < %zu)", d_scratch ? scratch_bytes : (size_t)0, P.bytes);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    uint8_t *base = (uint8_t *)(((uintptr_t)d_scratch + 255) & ~(uintptr_t)255);
+    uint64_t *incl = (uint64_t *)(base + P.incl), *sums = (uint64_t *)(base + P.sums);
+    uint32_t *err = (uint32_t *)(base + P.flags);
+    const bool timed = c->ktiming && c->kev_b[0];
+    if (timed) (void)hipEventRecord(c->kev_b[0], st);
+    HIPCHK(c, hipMemsetAsync(err, 0, 256, st));
+    const PiSrcStart start = { d_text };
+    dp_scan(st, start, n_bytes, sums, incl);
+    uint64_t total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, incl + (n_bytes - 1), 8, hipMemcpyDeviceToHost, st));
+    { int rcw = wait_stream(c, st, "brx_paf_scan (line starts)"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    const uint64_t n = max_lines && max_lines < total ? max_lines : total;
+    if (n >= (1ull << 31)) return fail(c, BRX_E_ARG, "brx_paf_scan: %llu lines: fewer than 2^31 in one call", (unsigned long long)n);
+    if (n > line_cap || !d_lines) {
+        c->output_needed = (size_t)n;
+        return fail(c, BRX_E_OUTPUT, "brx_paf_scan: room for %llu records, %llu lines", (unsigned long long)(d_lines ? line_cap : 0), (unsigned long long)n);
+    }
+    hipLaunchKernelGGL(k_pi_starts, dim3((uint32_t)((n_bytes + BRX_PI_THREADS - 1) / BRX_PI_THREADS)), dim3(BRX_PI_THREADS), 0, st, start, n_bytes, (const uint64_t *)incl, n, d_lines);
+    hipLaunchKernelGGL(k_pi_lines, dim3((uint32_t)n), dim3(64), 0, st, d_text, n_bytes, d_lines, err);
+    uint32_t bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, err, 4, hipMemcpyDeviceToHost, st));
+    if (timed) (void)hipEventRecord(c->kev_b[1], st);
+    { int rcw = wait_stream(c, st, "brx_paf_scan"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    if (timed) HIPCHK(c, hipEventElapsedTime(&c->loader_ms[0], c->kev_b[0], c->kev_b[1]));
+    if (bad) return fail(c, BRX_E_ARG, "brx_paf_scan: a line of 2^32 bytes or more");
+    *n_lines = n;
+    return BRX_OK;
+}
+
+extern "C" int brx_align_pack(brx_ctx *c, const brx_pack_job *job, void *hip_stream) {
+    if (!c || !job) return BRX_E_ARG;
+    const brx_pack_job j = *job;
+    if (j.n_align == 0) return BRX_OK;
+    if (!j.d_align || !j.d_align_part_off || !j.d_align_col_off || !j.d_align_read_off || !j.d_align_ref_off)
+        return fail(c, BRX_E_ARG, "brx_align_pack: d_align or an offset array is NULL");
+    if (!j.d_text || !j.d_reftext || !j.d_complement || !j.d_part_type || !j.d_part_len || !j.d_part_col || !j.d_part_read || !j.d_part_ref || !j.d_ref || !j.d_flags)
+        return fail(c, BRX_E_ARG, "brx_align_pack: a text, the complement table, an output array or d_flags is NULL");
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool timed = c->ktiming && c->kev_b[0];
+    if (timed) (void)hipEventRecord(c->kev_b[0], st);
+    hipLaunchKernelGGL(k_pi_pack, dim3(j.n_align), dim3(64), 0, st, j, j.d_flags);
+    if (timed) (void)hipEventRecord(c->kev_b[1], st);
+    uint32_t bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, j.d_flags, 4, hipMemcpyDeviceToHost, st));
+    { int rcw = wait_stream(c, st, "brx_align_pack"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    if (timed) HIPCHK(c, hipEventElapsedTime(&c->loader_ms[1], c->kev_b[0], c->kev_b[1]));
+    if (bad) return fail(c, BRX_E_ARG, "brx_align_pack: an alignment's descriptor does not fit its CIGAR, the texts or the offset arrays");
     return BRX_OK;
 }

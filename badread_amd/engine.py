@@ -153,6 +153,29 @@ WINDOW_STAT_DTYPE = np.dtype([('n', '<u4'), ('err_min', '<u4'), ('err_max', '<u4
 assert WINDOW_STAT_DTYPE.itemsize == 40
 
 
+class BrxPackJob(ctypes.Structure):
+    """brx_pack_job of include/brx.h"""
+    _fields_ = [('n_align', ctypes.c_uint32), ('reserved', ctypes.c_uint32),
+                ('d_text', ctypes.c_void_p), ('n_text', ctypes.c_uint64), ('d_reftext', ctypes.c_void_p), ('n_reftext', ctypes.c_uint64),
+                ('d_complement', ctypes.c_void_p), ('d_align', ctypes.c_void_p),
+                ('d_align_part_off', ctypes.c_void_p), ('d_align_col_off', ctypes.c_void_p),
+                ('d_align_read_off', ctypes.c_void_p), ('d_align_ref_off', ctypes.c_void_p),
+                ('d_part_type', ctypes.c_void_p), ('d_part_len', ctypes.c_void_p),
+                ('d_part_col', ctypes.c_void_p), ('d_part_read', ctypes.c_void_p), ('d_part_ref', ctypes.c_void_p),
+                ('d_ref', ctypes.c_void_p), ('d_flags', ctypes.c_void_p)]
+
+
+# brx_paf_line and brx_pack_align of include/brx.h
+PAF_IRREGULAR = 1
+PAF_LINE_DTYPE = np.dtype([('line_off', '<u8'), ('line_len', '<u4'), ('flags', '<u4'), ('qname_len', '<u4'), ('tname_off', '<u4'),
+                           ('tname_len', '<u4'), ('cigar_off', '<u4'), ('cigar_len', '<u4'), ('n_parts', '<u4'), ('max_indel', '<u4'),
+                           ('strand', '<u4'), ('ints', '<u8', (6,)), ('as', '<i8'), ('sum_m', '<u8'), ('sum_i', '<u8'), ('sum_d', '<u8'),
+                           ('first_d', '<u8'), ('last_d', '<u8')])
+PACK_ALIGN_DTYPE = np.dtype([('cigar_off', '<u8'), ('cigar_len', '<u4'), ('n_parts', '<u4'), ('sum_m', '<u8'), ('sum_i', '<u8'),
+                             ('sum_d', '<u8'), ('ref_off', '<u8'), ('ref_len', '<u8'), ('reversed', '<u4'), ('reserved', '<u4')])
+assert PAF_LINE_DTYPE.itemsize == 144 and PACK_ALIGN_DTYPE.itemsize == 64
+
+
 class BrxKernelStat(ctypes.Structure):
     _fields_ = [('launches', ctypes.c_uint32), ('ms', ctypes.c_float), ('bases', ctypes.c_double)]
 
@@ -361,6 +384,15 @@ def bind_library(lib):
     lib.brx_window_means.argtypes = [ctypes.c_void_p, ctypes.POINTER(BrxWindowJob), ctypes.c_void_p]
     lib.brx_window_last.restype = ctypes.c_int
     lib.brx_window_last.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float * 4)]
+    lib.brx_paf_scan_scratch.restype = ctypes.c_size_t
+    lib.brx_paf_scan_scratch.argtypes = [ctypes.c_uint64]
+    lib.brx_paf_scan.restype = ctypes.c_int
+    lib.brx_paf_scan.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                 ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.brx_align_pack.restype = ctypes.c_int
+    lib.brx_align_pack.argtypes = [ctypes.c_void_p, ctypes.POINTER(BrxPackJob), ctypes.c_void_p]
+    lib.brx_loader_last.restype = ctypes.c_int
+    lib.brx_loader_last.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float * 2)]
     lib.brx_bgzf_device_bound.restype = ctypes.c_size_t
     lib.brx_bgzf_device_bound.argtypes = [ctypes.c_size_t]
     lib.brx_bgzf_device_scratch.restype = ctypes.c_size_t
@@ -455,6 +487,10 @@ class HipEngine(EngineBase):
             raise BrxError(rc, self.lib.brx_last_error(self.ctx).decode('latin-1', 'replace'))
 
     def _upload(self, arr):
+        if isinstance(arr, self.torch.Tensor):               # already there (what align_pack made): as it is
+            if arr.device.type != self.device.type or not arr.is_contiguous() or arr.numel() == 0:
+                raise ValueError('a tensor given to the engine must be contiguous, not empty and on its device')
+            return arr.data_ptr(), arr
         arr = np.ascontiguousarray(arr)
         raw = arr.view(np.uint8).reshape(-1) if arr.dtype.fields is None else np.frombuffer(arr.tobytes(), dtype=np.uint8)
         if raw.size == 0:
@@ -844,6 +880,72 @@ class HipEngine(EngineBase):
         h_stats = np.frombuffer(stats.cpu().numpy().tobytes(), dtype=WINDOW_STAT_DTYPE)[:job.n_align]
         return (h_stats, err_sum[:n_windows].cpu().numpy().view(np.uint32) if err_sum is not None else None,
                 qual_sum[:n_windows].cpu().numpy() if qual_sum is not None else None)
+
+    def paf_scan(self, text, max_lines=0, cap=None):
+        """brx_paf_scan: PAF text as a uint8 tensor on this engine's device -> a numpy array of PAF_LINE_DTYPE, one record per line (the
+        first max_lines of them; 0: all).  `cap`: the records of the first buffer (default: one per 256 bytes of text); E_OUTPUT costs
+        one retry with the size the library names."""
+        torch = self.torch
+        n = int(text.numel())
+        if n == 0:
+            return np.zeros(0, dtype=PAF_LINE_DTYPE)
+        max_lines = max(int(max_lines or 0), 0)
+        cap = int(cap) if cap is not None else n // 256 + 64
+        if max_lines:
+            cap = min(cap, max_lines)
+        scratch = torch.empty(int(self.lib.brx_paf_scan_scratch(n)), dtype=torch.uint8, device=self.device)
+        got = ctypes.c_uint64(0)
+        for _ in range(2):
+            lines = torch.zeros(max(cap, 1) * PAF_LINE_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+            rc = self.lib.brx_paf_scan(self.ctx, ctypes.c_void_p(text.data_ptr()), n, max_lines, ctypes.c_void_p(lines.data_ptr()), cap,
+                                       ctypes.byref(got), ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), self._stream())
+            if rc != E_OUTPUT:
+                break
+            cap = int(self.lib.brx_output_needed(self.ctx))
+        self._check(rc)
+        return np.frombuffer(lines[:got.value * PAF_LINE_DTYPE.itemsize].cpu().numpy().tobytes(), dtype=PAF_LINE_DTYPE)
+
+    def align_pack(self, text, reftext, complement, aligns, part_off, col_off, read_off, ref_off):
+        """brx_align_pack: the part arrays and reference slices of model_builder.Job as tensors on this engine's device.  text / reftext /
+        complement: uint8 tensors there (the PAF text, the contigs back to back, the 256-byte table); aligns: PACK_ALIGN_DTYPE records;
+        the four offset arrays: numpy uint64, one entry more than there are alignments.  Returns a dict: part_type, part_len, part_col,
+        part_read, part_ref, ref -- never empty: as in Job, an array without an entry holds one 0."""
+        torch = self.torch
+        dev = self.device
+        n_align = len(aligns)
+        n_parts, n_ref = int(part_off[-1]), int(ref_off[-1])
+        out = dict(part_type=torch.zeros(max(n_parts, 1), dtype=torch.uint8, device=dev),
+                   part_len=torch.zeros(max(n_parts, 1), dtype=torch.int32, device=dev),
+                   part_col=torch.zeros(max(n_parts, 1), dtype=torch.int64, device=dev),
+                   part_read=torch.zeros(max(n_parts, 1), dtype=torch.int64, device=dev),
+                   part_ref=torch.zeros(max(n_parts, 1), dtype=torch.int64, device=dev),
+                   ref=torch.zeros(max(n_ref, 1), dtype=torch.uint8, device=dev))
+        if n_align == 0:
+            return out
+        keep = []
+
+        def up(arr):
+            ptr, t = self._upload(arr)
+            keep.append(t)
+            return ptr
+        flags = torch.zeros(4, dtype=torch.int32, device=dev)
+        s = BrxPackJob()
+        s.n_align = n_align
+        s.d_text, s.n_text, s.d_reftext, s.n_reftext = up(text), int(text.numel()), up(reftext), int(reftext.numel())
+        s.d_complement, s.d_align = up(complement), up(np.ascontiguousarray(aligns, dtype=PACK_ALIGN_DTYPE))
+        s.d_align_part_off, s.d_align_col_off = up(part_off.astype(np.uint64)), up(col_off.astype(np.uint64))
+        s.d_align_read_off, s.d_align_ref_off = up(read_off.astype(np.uint64)), up(ref_off.astype(np.uint64))
+        s.d_part_type, s.d_part_len = out['part_type'].data_ptr(), out['part_len'].data_ptr()
+        s.d_part_col, s.d_part_read, s.d_part_ref = out['part_col'].data_ptr(), out['part_read'].data_ptr(), out['part_ref'].data_ptr()
+        s.d_ref, s.d_flags = out['ref'].data_ptr(), flags.data_ptr()
+        self._check(self.lib.brx_align_pack(self.ctx, ctypes.byref(s), self._stream()))
+        return out
+
+    def loader_last(self):
+        """ms of the last paf_scan and the last align_pack under set_kernel_timing."""
+        ms = (ctypes.c_float * 2)()
+        self._check(self.lib.brx_loader_last(self.ctx, ctypes.byref(ms)))
+        return dict(zip(('scan', 'pack'), [float(x) for x in ms]))
 
     def window_last(self):
         """ms of the kernels of the last window_means under set_kernel_timing: errors, scans, stats, values."""

@@ -10,6 +10,9 @@ hash table of (key, count, earliest window) and the few windows a 64-bit key can
 text written to stdout is the reference's, byte for byte: alternatives and cigars with equal counts keep the order in
 which the reference's loops would first have met them (Python dict order + stable sort), reproduced from the earliest
 window recorded per key.
+
+With --gpu-loader (README: The device loader) the PAF is parsed by brx_paf_scan (alignment.load_alignments_device) and the part arrays and
+reference slices are written by brx_align_pack (Job.packed); the host then only joins the read slices.  Same text, same exits.
 """
 import collections
 import itertools
@@ -18,8 +21,8 @@ import sys
 
 import numpy as np
 
-from .alignment import load_alignments
-from .misc import float_to_str, load_fasta, load_fastq, only_acgt, reverse_complement
+from .alignment import DeviceAlignments, load_alignments, load_alignments_device
+from .misc import _COMPLEMENT, float_to_str, load_fasta, load_fastq, only_acgt, reverse_complement
 
 _TYPE = {'M': 0, 'I': 1, 'D': 2}
 EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -74,6 +77,47 @@ class Job(object):
         self.align_read_off = np.array(a_read, dtype=np.uint64)      # where each alignment's read slice begins in seq / qual
         self.n_align, self.n_cols = len(alignments), col
 
+    @classmethod
+    def packed(cls, engine, refs, reads, packed, first, end):
+        """The same job for packed[first:end] of a DeviceAlignments (--gpu-loader): seq and qual joined here as above, the part arrays
+        and ref written on the device by brx_align_pack from the CIGAR text that already lies there -- tensors, which model_count and
+        window_means take as they are.  The checks read the scan records (sum_m / sum_i / sum_d) instead of walking parts; slices is
+        made per alignment when a spill path asks for one."""
+        self = cls.__new__(cls)
+        alignments, rec = list.__getitem__(packed, slice(first, end)), packed.rec[first:end]
+        reftext, ref_at = _device_reference(engine, refs, packed)
+        n = len(alignments)
+        seqs, quals = [], []
+        read_len, ref_off, ref_len = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+        used_read, used_ref = (rec['sum_m'] + rec['sum_i']).tolist(), (rec['sum_m'] + rec['sum_d']).tolist()
+        for k, a in enumerate(alignments):
+            check_alignment_matches_read_and_refs(a, reads, refs)
+            read_seq, read_qual = (x[a.read_start:a.read_end] for x in reads[a.read_name])
+            lo, hi, _ = slice(a.ref_start, a.ref_end).indices(len(refs[a.ref_name]))           # Python's clipping rule
+            if used_read[k] > len(read_seq) or used_ref[k] > max(hi - lo, 0) or len(read_qual) < len(read_seq):
+                sys.exit(f'Error: the CIGAR of {a!r} runs past its read or reference range')
+            seqs.append(read_seq); quals.append(read_qual[:len(read_seq)])
+            read_len[k], ref_off[k], ref_len[k] = len(read_seq), ref_at[a.ref_name] + lo, max(hi - lo, 0)
+        enc = lambda parts_: np.frombuffer(''.join(parts_).encode('latin-1') or b'\0', dtype=np.uint8)
+        self.seq, self.qual = enc(seqs), enc(quals)
+        offsets = lambda x: np.concatenate((np.zeros(1, dtype=np.uint64), np.cumsum(x, dtype=np.uint64)))
+        self.align_part_off = offsets(rec['n_parts'])
+        self.align_col_off = offsets(rec['sum_m'] + rec['sum_i'] + rec['sum_d'])
+        self.align_read_off = offsets(read_len)
+        self.align_ref_off = offsets(ref_len)
+        from .engine import PACK_ALIGN_DTYPE
+        desc = np.zeros(n, dtype=PACK_ALIGN_DTYPE)
+        for field in ('cigar_off', 'cigar_len', 'n_parts', 'sum_m', 'sum_i', 'sum_d', 'reversed'):
+            desc[field] = rec[field]
+        desc['ref_off'], desc['ref_len'] = ref_off, ref_len
+        out = engine.align_pack(packed.text, reftext, _device_complement(engine, packed), desc, self.align_part_off, self.align_col_off,
+                                self.align_read_off, self.align_ref_off)
+        self.part_type, self.part_len, self.ref = out['part_type'], out['part_len'], out['ref']
+        self.part_col, self.part_read, self.part_ref = out['part_col'], out['part_read'], out['part_ref']
+        self.n_align, self.n_cols = n, int(self.align_col_off[-1])
+        self.slices = _LazySlices(refs, reads, alignments)
+        return self
+
     def gapped(self, a, gap):
         """align_sequences (alignment.py:101-132) for alignment a: gapped read, quality, reference strings."""
         read_seq, read_qual, ref_seq, parts = self.slices[a]
@@ -88,6 +132,69 @@ class Job(object):
             if t != 'I':
                 fp += n
         return ''.join(read), ''.join(qual), ''.join(ref)
+
+
+class _LazySlices(object):
+    """Job.slices of a packed job: an entry is made when it is asked for."""
+
+    def __init__(self, refs, reads, alignments):
+        self.refs, self.reads, self.alignments = refs, reads, alignments
+
+    def __len__(self):
+        return len(self.alignments)
+
+    def __getitem__(self, k):
+        a = self.alignments[k]
+        read_seq, read_qual = (x[a.read_start:a.read_end] for x in self.reads[a.read_name])
+        ref_seq = self.refs[a.ref_name][a.ref_start:a.ref_end]
+        if a.strand == '-':
+            ref_seq = reverse_complement(ref_seq)
+        return read_seq, read_qual, ref_seq, [(n, t) for n, t in a.cigar_parts if t in _TYPE]
+
+
+def _device_reference(engine, refs, packed):
+    """(the contigs' text back to back on the device, {contig: where it begins}): uploaded once per command, kept on `packed`."""
+    held = getattr(packed, '_reference', None)
+    if held is None or held[0] is not refs:
+        at, total = {}, 0
+        for name, seq in refs.items():
+            at[name] = total
+            total += len(seq)
+        text = np.frombuffer(''.join(refs.values()).encode('latin-1') or b'\0', dtype=np.uint8)
+        held = packed._reference = (refs, engine._upload(text)[1], at)
+    return held[1], held[2]
+
+
+def _device_complement(engine, packed):
+    """misc._COMPLEMENT as the 256 bytes brx_align_pack reads: N for every byte it does not name (reverse_complement)."""
+    held = getattr(packed, '_complement', None)
+    if held is None:
+        table = np.full(256, ord('N'), dtype=np.uint8)
+        for base, other in _COMPLEMENT.items():
+            table[ord(base)] = ord(other)
+        held = packed._complement = engine._upload(table)[1]
+    return held
+
+
+def _load(args, engine, output):
+    """The alignments of a model command: load_alignments, or with --gpu-loader its device twin."""
+    if getattr(args, 'gpu_loader', False):
+        return load_alignments_device(args.alignment, engine, args.max_alignments, output=output)
+    return load_alignments(args.alignment, args.max_alignments, output=output)
+
+
+def _job(engine, refs, reads, alignments):
+    if isinstance(alignments, DeviceAlignments):
+        return Job.packed(engine, refs, reads, alignments, 0, len(alignments))
+    return Job(refs, reads, alignments)
+
+
+def _engine(args, engine):
+    """The engine before the alignments are loaded when the loader needs it, else where it always was made."""
+    if engine is None and getattr(args, 'gpu_loader', False):
+        from .engine import default_engine
+        engine = default_engine()
+    return engine
 
 
 def _table(engine, kind, job, k, max_del, n_ksizes, first_bits=16):
@@ -143,7 +250,8 @@ def make_error_model(args, output=sys.stderr, dot_interval=1000, engine=None, st
     stdout = stdout or sys.stdout
     refs, _, _, _, _ = load_fasta(args.reference)
     reads = load_fastq(args.reads, output=output)
-    alignments = load_alignments(args.alignment, args.max_alignments, output=output)
+    engine = _engine(args, engine)
+    alignments = _load(args, engine, output)
     if len(alignments) == 0:
         sys.exit('Error: no usable alignments')
     k = args.k_size
@@ -153,7 +261,7 @@ def make_error_model(args, output=sys.stderr, dot_interval=1000, engine=None, st
         from .engine import default_engine
         engine = default_engine()
     print('Processing alignments', end='', file=output, flush=True)
-    found = count_error_model(engine, Job(refs, reads, alignments), k)
+    found = count_error_model(engine, _job(engine, refs, reads, alignments), k)
     print('.' * (len(alignments) // dot_interval), file=output, flush=True)
     by_kmer = collections.defaultdict(list)
     for (ref_kmer, read_kmer), (n, rank) in found.items():
@@ -225,7 +333,8 @@ def make_qscore_model(args, output=sys.stderr, dot_interval=1000, engine=None, s
     stdout = stdout or sys.stdout
     refs, _, _, _, _ = load_fasta(args.reference)
     reads = load_fastq(args.reads, output=output)
-    alignments = load_alignments(args.alignment, args.max_alignments, output=output)
+    engine = _engine(args, engine)
+    alignments = _load(args, engine, output)
     if len(alignments) == 0:
         sys.exit('Error: no usable alignments')
     assert args.k_size % 2 == 1
@@ -236,7 +345,7 @@ def make_qscore_model(args, output=sys.stderr, dot_interval=1000, engine=None, s
         from .engine import default_engine
         engine = default_engine()
     print('Processing alignments', end='', file=output, flush=True)
-    per_cigar = count_qscore_model(engine, Job(refs, reads, alignments), args.k_size, args.max_del)
+    per_cigar = count_qscore_model(engine, _job(engine, refs, reads, alignments), args.k_size, args.max_del)
     print('.' * (len(alignments) // dot_interval), file=output, flush=True)
     overall = collections.Counter()
     for cigar, (_, qs) in per_cigar.items():

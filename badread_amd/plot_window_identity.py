@@ -14,7 +14,8 @@ The doubles are made from those here with the reference's own expressions, so th
     position[i] = read_start + i + W // 2     identity[i] = 100.0 * (1.0 - S[i] / W)     quality[i] = Q[i] / W
 
 Additive: --summary PATH (one TSV line per alignment, no window values leave the device), --save DIR (one PNG per alignment) and
---max_alignments N.  Drawing needs matplotlib, which is imported only where a plot is drawn.
+--max_alignments N.  Drawing needs matplotlib, which is imported only where a plot is drawn.  --gpu-loader: the PAF parsed and every
+chunk packed on the device (alignment.load_alignments_device, model_builder.Job.packed), the same output.
 """
 import contextlib
 import itertools
@@ -24,7 +25,7 @@ import sys
 
 import numpy as np
 
-from .alignment import load_alignments
+from .alignment import NO_D, DeviceAlignments, load_alignments, load_alignments_device
 from .misc import load_fasta, load_fastq
 from .model_builder import Job, check_alignment_matches_read_and_refs
 
@@ -72,6 +73,29 @@ def _check_alignment(a, reads, refs, qual):
     return length
 
 
+def _check_packed(a, rec, reads, refs, qual):
+    """_check_alignment from the scan record of a (--gpu-loader): the same exits in the same order.  A D part with no read base behind
+    it: the D with the most read bases in front of it is the last one in file order for '+' and, the list being read backwards, the
+    first one for '-'."""
+    check_alignment_matches_read_and_refs(a, reads, refs)
+    length = len(range(*slice(a.read_start, a.read_end).indices(len(reads[a.read_name][0]))))
+    first_d, last_d, used_read = int(rec['first_d']), int(rec['last_d']), int(rec['sum_m']) + int(rec['sum_i'])
+    if first_d != NO_D and (used_read - first_d >= length if a.strand == '-' else last_d >= length):
+        sys.exit(f'Error: the CIGAR of {a!r} ends in a deletion with no read base after it')
+    if used_read + int(rec['sum_d']) >= 1 << 31:
+        sys.exit(f'Error: the CIGAR of {a!r} has 2^31 or more columns')
+    if qual and 223 * length >= 1 << 31:
+        sys.exit(f'Error: the read slice of {a!r} is too long for --qual (32-bit quality sums)')
+    return length
+
+
+def check_alignments(alignments, reads, refs, qual):
+    """The lengths of the read slices of all alignments, every alignment checked on the way."""
+    if isinstance(alignments, DeviceAlignments):
+        return [_check_packed(a, rec, reads, refs, qual) for a, rec in zip(alignments, alignments.rec)]
+    return [_check_alignment(a, reads, refs, qual) for a in alignments]
+
+
 def chunks(lengths, limit):
     """(first, end) index ranges: as many consecutive alignments as hold at most `limit` read bases, at least one."""
     first, held = 0, 0
@@ -89,9 +113,11 @@ def window_means(engine, refs, reads, alignments, window, qual, values=False, le
     engine.WINDOW_STAT_DTYPE, the sums arrays of stat['n'] integers or None (values=False; qual_sum also without qual).  Every
     alignment is checked before the first chunk is shipped."""
     if lengths is None:
-        lengths = [_check_alignment(a, reads, refs, qual) for a in alignments]
+        lengths = check_alignments(alignments, reads, refs, qual)
+    device = isinstance(alignments, DeviceAlignments)
     for first, end in chunks(lengths, PLOT_CHUNK_BASES):
-        stats, err_sum, qual_sum = engine.window_means(Job(refs, reads, alignments[first:end]), window, qual, values)
+        job = Job.packed(engine, refs, reads, alignments, first, end) if device else Job(refs, reads, alignments[first:end])
+        stats, err_sum, qual_sum = engine.window_means(job, window, qual, values)
         off = np.concatenate(([0], np.cumsum(stats['n'].astype(np.int64))))
         for k in range(end - first):
             lo, hi = int(off[k]), int(off[k + 1])
@@ -155,8 +181,14 @@ def plot_window_identity(args, output=sys.stdout, engine=None, stdout=None):
         sys.exit(f'Error: the directory of --summary {summary} does not exist')
     reads = load_fastq(args.reads, output=output)
     refs, _, _, _, _ = load_fasta(args.reference)
-    alignments = load_alignments(args.alignment, getattr(args, 'max_alignments', None), output=output)
-    lengths = [_check_alignment(a, reads, refs, qual) for a in alignments]
+    if getattr(args, 'gpu_loader', False):
+        if engine is None:
+            from .engine import default_engine
+            engine = default_engine()
+        alignments = load_alignments_device(args.alignment, engine, getattr(args, 'max_alignments', None), output=output)
+    else:
+        alignments = load_alignments(args.alignment, getattr(args, 'max_alignments', None), output=output)
+    lengths = check_alignments(alignments, reads, refs, qual)
     draw = save is not None or not args.no_plot
     plt = _pyplot(save is not None) if draw else None
     if save is not None:

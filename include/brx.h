@@ -378,6 +378,73 @@ int brx_window_means(brx_ctx *ctx, const brx_window_job *job, void *hip_stream);
 /* ms between HIP events of the last brx_window_means on ctx that ran under brx_set_kernel_timing: errors, the scans, statistics, values */
 int brx_window_last(const brx_ctx *ctx, float ms[4]);
 
+/* ------------------------------------------------------------------ the device loader (README: The device loader (`--gpu-loader`))
+ * What load_alignments and model_builder.Job do per CIGAR part, on the device; the host keeps what is O(1) per line or alignment.
+ *
+ * brx_paf_scan: n_bytes of PAF text in device memory -> one brx_paf_line per line (a byte is a line start if it is byte 0 or follows '\n';
+ * a last line without '\n' is a line, the empty piece behind a final '\n' is not).  max_lines: 0 = all; the lines beyond it are neither
+ * parsed nor able to flag anything.  *n_lines = the lines written.  d_scratch: brx_paf_scan_scratch(n_bytes) bytes of device memory.
+ * A record holds line_off / line_len (without the '\n'), the spans of field 0 (qname: line_off, qname_len) and field 5 (tname), the strand
+ * byte, ints[] = the fields 2, 3, 7, 8, 9, 10, `as` = the value of the LAST field that begins AS:i:, cigar_off / cigar_len = the value of
+ * the LAST field that begins cg:Z: (all fields count, the first twelve included; offsets from line_off), and of that CIGAR's M / I / D
+ * parts (every other letter is a part that is dropped): n_parts, sum_m / sum_i / sum_d, max_indel (the longest I or D part, 0 if none),
+ * first_d / last_d (the M + I bases in front of the first / last D part in file order, ~0 without one).
+ * A line is regular when every byte is '\t' or in 0x21..0x7e and the first and last are not '\t'; it has at least 11 fields and a strand
+ * of one byte; the six integers are [0-9]{1,18} and field 10 is not zero; a cg:Z: and an AS:i: field exist; every AS:i: value is
+ * -?[0-9]{1,18}; the CIGAR of the last cg:Z: field is ([0-9]{1,9}[A-Za-z])+.  Any other line carries
+ * BRX_PAF_IRREGULAR in flags and nothing else of its record but line_off and line_len is promised: the host parses it.
+ *   BRX_E_OUTPUT + brx_output_needed()   line_cap is too small (needed: the number of records); nothing written
+ *   BRX_E_ARG                            a NULL argument that is needed; a line of 2^32 bytes or more
+ *   BRX_E_SCRATCH + brx_scratch_needed() scratch_bytes is too small
+ * Zero bytes is a valid call (no line).  Synchronous on `hip_stream`; takes nothing from the simulate pipeline's state.               */
+#define BRX_PAF_IRREGULAR 1u
+typedef struct {
+    uint64_t line_off;
+    uint32_t line_len, flags;
+    uint32_t qname_len, tname_off, tname_len, cigar_off, cigar_len, n_parts, max_indel, strand;
+    uint64_t ints[6];
+    int64_t as;
+    uint64_t sum_m, sum_i, sum_d, first_d, last_d;
+} brx_paf_line;
+size_t brx_paf_scan_scratch(uint64_t n_bytes);
+int brx_paf_scan(brx_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint64_t max_lines, brx_paf_line *d_lines, uint64_t line_cap,
+                 uint64_t *n_lines, void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* brx_align_pack: the arrays brx_model_count and brx_window_means read, written from the CIGAR text of n_align chosen alignments, a wave
+ * per alignment.  Per alignment (d_align): its CIGAR's span in d_text -- ([0-9]{1,10}[A-Za-z])+ with every length below 2^32, or empty --,
+ * the n_parts and sums brx_paf_scan gave for it, `reversed` ('-' strand), and its reference slice's start and length in d_reftext (the
+ * contigs' text back to back).  d_align_part_off / d_align_col_off / d_align_read_off / d_align_ref_off (n_align + 1 each): where the
+ * alignment's parts, columns, read slice and reference slice begin; part_off and ref_off advance by n_parts and ref_len, read_off by the
+ * clipped read slice's length, as in model_builder.Job.  Output: d_part_type (0 / 1 / 2), d_part_len, d_part_col / d_part_read /
+ * d_part_ref (a part's first column / read base / reference base, from the alignment's bases) and d_ref (the slice, or for a reversed
+ * alignment its reverse through d_complement, 256 bytes).  The part with file index i of a reversed alignment lands at n_parts - 1 - i
+ * with the mirrored offsets.  An alignment without parts, or without reference bases, is valid; so are zero alignments.
+ *   BRX_E_ARG   a NULL array that is needed; a descriptor that leaves the texts, disagrees with the offset arrays or with its CIGAR
+ *               (d_flags[0] is then 1, that alignment's outputs are not complete and nothing is stored outside its own ranges)
+ * No global scan, no atomics, no waiting between workgroups.  Synchronous on `hip_stream`.                                              */
+typedef struct {
+    uint64_t cigar_off;
+    uint32_t cigar_len, n_parts;
+    uint64_t sum_m, sum_i, sum_d;
+    uint64_t ref_off, ref_len;
+    uint32_t reversed, reserved;
+} brx_pack_align;
+typedef struct {
+    uint32_t n_align, reserved;
+    const uint8_t *d_text; uint64_t n_text;
+    const uint8_t *d_reftext; uint64_t n_reftext;
+    const uint8_t *d_complement;
+    const brx_pack_align *d_align;
+    const uint64_t *d_align_part_off, *d_align_col_off, *d_align_read_off, *d_align_ref_off;
+    uint8_t *d_part_type; uint32_t *d_part_len;
+    uint64_t *d_part_col, *d_part_read, *d_part_ref;
+    uint8_t *d_ref;
+    uint32_t *d_flags;                 /* [1], preset to 0: set where a descriptor is refused */
+} brx_pack_job;
+int brx_align_pack(brx_ctx *ctx, const brx_pack_job *job, void *hip_stream);
+/* ms between HIP events of the last brx_paf_scan and brx_align_pack on ctx that ran under brx_set_kernel_timing */
+int brx_loader_last(const brx_ctx *ctx, float ms[2]);
+
 /* ---- output stage: the FASTQ bytes of a batch as gzip members, made on the device ----
  * Replaces the `| gzip` the reference's users put behind /root/reference/badread/simulate.py:73-82 (print of the
  * record text).  d_in: n_bytes of text in device memory.  d_block_off: n_blocks + 1 ascending byte offsets (device
