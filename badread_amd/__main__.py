@@ -167,8 +167,11 @@ def parse_args(argv):
                                                                 'included in the model')
     opt.add_argument('--max_output', type=int, default=10000, help='The outputted model will be limited to this many lines')
     loader = dict(action='store_true', dest='gpu_loader', help='Parse the PAF\'s CIGARs and pack the alignments on the GPU (same output)')
+    reads = dict(action='store_true', dest='gpu_reads', help='Parse the FASTQ and pack the read slices on the GPU (same output; needs --gpu-loader)')
     for sub in (em, qm):
-        sub.add_argument_group('MI355X', description='Additive options (no effect on the model)').add_argument('--gpu-loader', **loader)
+        group = sub.add_argument_group('MI355X', description='Additive options (no effect on the model)')
+        group.add_argument('--gpu-loader', **loader)
+        group.add_argument('--gpu-reads', **reads)
     _add_help_group(em)
     _add_help_group(qm)
     # plot: flags and defaults of the reference (__main__.py:208-228) and a group of additive ones
@@ -189,6 +192,7 @@ def parse_args(argv):
                      help='Save one PNG per alignment to DIR/<index>_<read name>.png instead of displaying it')
     gpu.add_argument('--max_alignments', type=int, help='Only use this many alignments of the PAF (default: use all alignments)')
     gpu.add_argument('--gpu-loader', **loader)
+    gpu.add_argument('--gpu-reads', **reads)
     _add_help_group(pl)
     for name in OUT_OF_SCOPE:
         sub = subparsers.add_parser(name, add_help=False, description=f'{name}: not part of the MI355X build')

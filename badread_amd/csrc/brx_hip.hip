@@ -29,6 +29,7 @@
 #include "brx_depth.h"
 #include "brx_window.h"
 #include "brx_pafin.h"
+#include "brx_fastqin.h"
 
 #define BRX_KEV_MAX 2048
 
@@ -93,6 +94,7 @@ struct brx_ctx {
     uint32_t depth_passes; float depth_ms[3];      /* the last brx_depth_bedgraph: its sort passes; ms of its sort, depth and text stages */
     float window_ms[4];                            /* the last brx_window_means under brx_set_kernel_timing: errors, scans, statistics, values */
     float loader_ms[2];                            /* the last brx_paf_scan and brx_align_pack under brx_set_kernel_timing */
+    float reads_ms[2];                             /* the last brx_fastq_scan and brx_reads_pack under brx_set_kernel_timing */
     char err[512];
 };
 
@@ -1673,5 +1675,105 @@ extern "C" int brx_align_pack(brx_ctx *c, const brx_pack_job *job, void *hip_str
     HIPCHK(c, hipGetLastError());
     if (timed) HIPCHK(c, hipEventElapsedTime(&c->loader_ms[1], c->kev_b[0], c->kev_b[1]));
     if (bad) return fail(c, BRX_E_ARG, "brx_align_pack: an alignment's descriptor does not fit its CIGAR, the texts or the offset arrays");
+    return BRX_OK;
+}
+
+/* ---- the device read loader (brx_fastqin.h) ---- */
+/* where brx_fastq_scan keeps what in its scratch: the scan's prefix per group of 16 bytes, the tile sums, the flags, the line starts */
+struct FqPlan { uint64_t n_groups; uint32_t n_tiles; size_t incl, sums, flags, lines, bytes; };
+static FqPlan fq_plan(uint64_t n_bytes, uint64_t n_lines) {
+    FqPlan p; p.n_groups = (n_bytes + 15) / 16; p.n_tiles = (uint32_t)((p.n_groups + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE);
+    size_t at = 0;
+    auto take = [&](uint64_t bytes) { const size_t here = at; at += (size_t)((bytes + 255) & ~(uint64_t)255); return here; };
+    p.incl = take(p.n_groups * 8); p.sums = take(((uint64_t)p.n_tiles + 1) * 8); p.flags = take(256); p.lines = take((n_lines + 1) * 8);
+    p.bytes = at + 256;                                  /* the caller's block may begin anywhere */
+    return p;
+}
+extern "C" size_t brx_fastq_scan_scratch(uint64_t n_bytes) { return fq_plan(n_bytes, n_bytes / 64 + 64).bytes; }
+extern "C" int brx_reads_last(const brx_ctx *c, float ms[2]) {
+    if (!c || !ms) return BRX_E_ARG;
+    memcpy(ms, c->reads_ms, sizeof(c->reads_ms));
+    return BRX_OK;
+}
+extern "C" int brx_fastq_scan(brx_ctx *c, const uint8_t *d_text, uint64_t n_bytes, brx_fastq_rec *d_recs, uint64_t rec_cap, uint64_t *n_recs,
+                              uint32_t *layout, void *d_scratch, size_t scratch_bytes, void *hip_stream) {
+    if (!c) return BRX_E_ARG;
+    if (!n_recs || !layout) return fail(c, BRX_E_ARG, "brx_fastq_scan: n_recs or layout is NULL");
+    *n_recs = 0; *layout = 0;
+    if (n_bytes == 0) return BRX_OK;
+    if (!d_text) return fail(c, BRX_E_ARG, "brx_fastq_scan: d_text is NULL");
+    if (n_bytes >= (1ull << 42)) return fail(c, BRX_E_ARG, "brx_fastq_scan: %llu bytes: fewer than 2^42 in one call", (unsigned long long)n_bytes);
+    const size_t least = brx_fastq_scan_scratch(n_bytes);
+    if (!d_scratch || scratch_bytes < least) {
+        c->scratch_needed = least;
+        return fail(c, BRX_E_SCRATCH, "brx_fastq_scan: scratch too small (%zu < %zu)", d_scratch ? scratch_bytes : (size_t)0, least);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    uint8_t *base = (uint8_t *)(((uintptr_t)d_scratch + 255) & ~(uintptr_t)255);
+    FqPlan P = fq_plan(n_bytes, 0);
+    uint64_t *incl = (uint64_t *)(base + P.incl), *sums = (uint64_t *)(base + P.sums);
+    uint32_t *flags = (uint32_t *)(base + P.flags);
+    const bool timed = c->ktiming && c->kev_b[0];
+    if (timed) (void)hipEventRecord(c->kev_b[0], st);
+    HIPCHK(c, hipMemsetAsync(flags, 0, 256, st));
+    const FqSrcStarts16 src = { d_text, n_bytes };
+    dp_scan(st, src, P.n_groups, sums, incl);
+    uint64_t n_lines = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_lines, incl + (P.n_groups - 1), 8, hipMemcpyDeviceToHost, st));
+    { int rcw = wait_stream(c, st, "brx_fastq_scan (line starts)"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    if (n_lines & 3u) { *layout = BRX_FQ_LINES; return BRX_OK; }
+    const uint64_t n = n_lines / 4;
+    if (n >= (1ull << 31)) return fail(c, BRX_E_ARG, "brx_fastq_scan: %llu records: fewer than 2^31 in one call", (unsigned long long)n);
+    if (n > rec_cap || !d_recs) {
+        c->output_needed = (size_t)n;
+        return fail(c, BRX_E_OUTPUT, "brx_fastq_scan: room for %llu records, %llu in the file", (unsigned long long)(d_recs ? rec_cap : 0), (unsigned long long)n);
+    }
+    P = fq_plan(n_bytes, n_lines);
+    if (scratch_bytes < P.bytes) {
+        c->scratch_needed = P.bytes;
+        return fail(c, BRX_E_SCRATCH, "brx_fastq_scan: scratch too small for %llu lines (%zu < %zu)", (unsigned long long)n_lines, scratch_bytes, P.bytes);
+    }
+    uint64_t *line_start = (uint64_t *)(base + P.lines);
+    hipLaunchKernelGGL(k_fq_starts, dim3((uint32_t)((P.n_groups + BRX_FQ_THREADS - 1) / BRX_FQ_THREADS)), dim3(BRX_FQ_THREADS), 0, st, src, P.n_groups, (const uint64_t *)incl, line_start, flags);
+    hipLaunchKernelGGL(k_fq_records, dim3((uint32_t)((n + BRX_FQ_THREADS - 1) / BRX_FQ_THREADS)), dim3(BRX_FQ_THREADS), 0, st, d_text, (const uint64_t *)line_start, n, d_recs, flags);
+    uint32_t got[3] = { 0, 0, 0 };
+    HIPCHK(c, hipMemcpyAsync(got, flags, sizeof(got), hipMemcpyDeviceToHost, st));
+    if (timed) (void)hipEventRecord(c->kev_b[1], st);
+    { int rcw = wait_stream(c, st, "brx_fastq_scan"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    if (timed) HIPCHK(c, hipEventElapsedTime(&c->reads_ms[0], c->kev_b[0], c->kev_b[1]));
+    if (got[2]) return fail(c, BRX_E_ARG, "brx_fastq_scan: a line of 2^32 bytes or more");
+    *layout = (got[0] ? BRX_FQ_HIGH : 0u) | (got[1] ? BRX_FQ_HEADER : 0u);
+    if (*layout == 0) *n_recs = n;
+    return BRX_OK;
+}
+
+extern "C" int brx_reads_pack(brx_ctx *c, const brx_reads_job *job, void *hip_stream) {
+    if (!c || !job) return BRX_E_ARG;
+    const brx_reads_job j = *job;
+    if (j.n_align == 0) return BRX_OK;
+    if (!j.d_seq_src || !j.d_qual_src || !j.d_align_read_off) return fail(c, BRX_E_ARG, "brx_reads_pack: a source or offset array is NULL");
+    if (!j.d_text || !j.d_seq || !j.d_qual || !j.d_flags) return fail(c, BRX_E_ARG, "brx_reads_pack: the text, an output array or d_flags is NULL");
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool timed = c->ktiming && c->kev_b[0];
+    if (timed) (void)hipEventRecord(c->kev_b[0], st);
+    hipLaunchKernelGGL(k_fq_check, dim3((j.n_align + BRX_FQ_THREADS - 1) / BRX_FQ_THREADS), dim3(BRX_FQ_THREADS), 0, st, j, j.d_flags);
+    uint32_t bad = 0;
+    uint64_t total = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, j.d_flags, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&total, j.d_align_read_off + j.n_align, 8, hipMemcpyDeviceToHost, st));
+    { int rcw = wait_stream(c, st, "brx_reads_pack (check)"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    if (bad) return fail(c, BRX_E_ARG, "brx_reads_pack: the offsets do not ascend from 0, or a source range leaves the text");
+    const uint64_t n_tiles = (total + BRX_FQ_TILE - 1) / BRX_FQ_TILE;
+    if (n_tiles >= (1ull << 31)) return fail(c, BRX_E_ARG, "brx_reads_pack: %llu read bases: fewer than 2^43 in one call", (unsigned long long)total);
+    if (n_tiles) hipLaunchKernelGGL(k_fq_pack, dim3((uint32_t)n_tiles), dim3(BRX_FQ_THREADS), 0, st, j, total, ((uintptr_t)j.d_text & 3u) == 0);
+    if (timed) (void)hipEventRecord(c->kev_b[1], st);
+    { int rcw = wait_stream(c, st, "brx_reads_pack"); if (rcw) return rcw; }
+    HIPCHK(c, hipGetLastError());
+    if (timed) HIPCHK(c, hipEventElapsedTime(&c->reads_ms[1], c->kev_b[0], c->kev_b[1]));
     return BRX_OK;
 }

@@ -174,6 +174,18 @@ PAF_LINE_DTYPE = np.dtype([('line_off', '<u8'), ('line_len', '<u4'), ('flags', '
 PACK_ALIGN_DTYPE = np.dtype([('cigar_off', '<u8'), ('cigar_len', '<u4'), ('n_parts', '<u4'), ('sum_m', '<u8'), ('sum_i', '<u8'),
                              ('sum_d', '<u8'), ('ref_off', '<u8'), ('ref_len', '<u8'), ('reversed', '<u4'), ('reserved', '<u4')])
 assert PAF_LINE_DTYPE.itemsize == 144 and PACK_ALIGN_DTYPE.itemsize == 64
+# brx_fastq_rec of include/brx.h, and the bits of brx_fastq_scan's layout word
+FQ_LINES, FQ_HEADER, FQ_HIGH = 1, 2, 4
+FASTQ_REC_DTYPE = np.dtype([('head_off', '<u8'), ('name_off', '<u4'), ('name_len', '<u4'), ('seq_off', '<u8'), ('qual_off', '<u8'),
+                            ('seq_len', '<u4'), ('qual_len', '<u4'), ('flags', '<u4'), ('reserved', '<u4')])
+assert FASTQ_REC_DTYPE.itemsize == 48
+
+
+class BrxReadsJob(ctypes.Structure):
+    """brx_reads_job of include/brx.h"""
+    _fields_ = [('n_align', ctypes.c_uint32), ('reserved', ctypes.c_uint32), ('d_text', ctypes.c_void_p), ('n_text', ctypes.c_uint64),
+                ('d_seq_src', ctypes.c_void_p), ('d_qual_src', ctypes.c_void_p), ('d_align_read_off', ctypes.c_void_p),
+                ('d_seq', ctypes.c_void_p), ('d_qual', ctypes.c_void_p), ('d_flags', ctypes.c_void_p)]
 
 
 class BrxKernelStat(ctypes.Structure):
@@ -393,6 +405,16 @@ def bind_library(lib):
     lib.brx_align_pack.argtypes = [ctypes.c_void_p, ctypes.POINTER(BrxPackJob), ctypes.c_void_p]
     lib.brx_loader_last.restype = ctypes.c_int
     lib.brx_loader_last.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float * 2)]
+    lib.brx_fastq_scan_scratch.restype = ctypes.c_size_t
+    lib.brx_fastq_scan_scratch.argtypes = [ctypes.c_uint64]
+    lib.brx_fastq_scan.restype = ctypes.c_int
+    lib.brx_fastq_scan.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                   ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p, ctypes.c_size_t,
+                                   ctypes.c_void_p]
+    lib.brx_reads_pack.restype = ctypes.c_int
+    lib.brx_reads_pack.argtypes = [ctypes.c_void_p, ctypes.POINTER(BrxReadsJob), ctypes.c_void_p]
+    lib.brx_reads_last.restype = ctypes.c_int
+    lib.brx_reads_last.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float * 2)]
     lib.brx_bgzf_device_bound.restype = ctypes.c_size_t
     lib.brx_bgzf_device_bound.argtypes = [ctypes.c_size_t]
     lib.brx_bgzf_device_scratch.restype = ctypes.c_size_t
@@ -945,6 +967,68 @@ class HipEngine(EngineBase):
         """ms of the last paf_scan and the last align_pack under set_kernel_timing."""
         ms = (ctypes.c_float * 2)()
         self._check(self.lib.brx_loader_last(self.ctx, ctypes.byref(ms)))
+        return dict(zip(('scan', 'pack'), [float(x) for x in ms]))
+
+    def fastq_scan(self, text, cap=None):
+        """brx_fastq_scan: FASTQ text as a uint8 tensor on this engine's device -> (a numpy array of FASTQ_REC_DTYPE, one record per four
+        lines, and the layout word).  A layout other than 0 (FQ_LINES | FQ_HEADER | FQ_HIGH) comes with no record: the host loads such a
+        file.  `cap`: the records of the first buffer (default: one per 1024 bytes of text); E_OUTPUT costs one retry with the size the
+        library names, and so does E_SCRATCH for a file of more than one line per 64 bytes."""
+        torch = self.torch
+        n = int(text.numel())
+        if n == 0:
+            return np.zeros(0, dtype=FASTQ_REC_DTYPE), 0
+        cap = int(cap) if cap is not None else n // 1024 + 64
+        room = int(self.lib.brx_fastq_scan_scratch(n))
+        got, layout = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        recs = scratch = None
+        for _ in range(3):
+            if scratch is None or scratch.numel() < room:
+                scratch = None
+                scratch = torch.empty(room, dtype=torch.uint8, device=self.device)
+            if recs is None or recs.numel() < cap * FASTQ_REC_DTYPE.itemsize:
+                recs = None
+                recs = torch.zeros(max(cap, 1) * FASTQ_REC_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+            rc = self.lib.brx_fastq_scan(self.ctx, ctypes.c_void_p(text.data_ptr()), n, ctypes.c_void_p(recs.data_ptr()), cap,
+                                         ctypes.byref(got), ctypes.byref(layout), ctypes.c_void_p(scratch.data_ptr()), scratch.numel(),
+                                         self._stream())
+            if rc == E_OUTPUT and cap < int(self.lib.brx_output_needed(self.ctx)):
+                cap = int(self.lib.brx_output_needed(self.ctx))
+            elif rc == E_SCRATCH and room < int(self.lib.brx_scratch_needed(self.ctx)):
+                room = int(self.lib.brx_scratch_needed(self.ctx))
+            else:
+                break
+        self._check(rc)
+        return np.frombuffer(recs[:got.value * FASTQ_REC_DTYPE.itemsize].cpu().numpy().tobytes(), dtype=FASTQ_REC_DTYPE), int(layout.value)
+
+    def reads_pack(self, text, seq_src, qual_src, read_off):
+        """brx_reads_pack: seq and qual of model_builder.Job as uint8 tensors on this engine's device.  text: the FASTQ text there;
+        seq_src / qual_src: where each alignment's read slice and its qualities begin in it; read_off: where they begin in the output,
+        one entry more than there are alignments (numpy uint64, all three).  Never empty: as in Job, an array without a base holds one 0."""
+        torch = self.torch
+        n_align, n_bases = len(seq_src), int(read_off[-1])
+        if n_align == 0 or n_bases == 0:
+            return tuple(torch.zeros(1, dtype=torch.uint8, device=self.device) for _ in range(2))
+        seq, qual = (torch.empty(n_bases, dtype=torch.uint8, device=self.device) for _ in range(2))
+        keep = []
+
+        def up(arr):
+            ptr, t = self._upload(arr)
+            keep.append(t)
+            return ptr
+        flags = torch.zeros(4, dtype=torch.int32, device=self.device)
+        s = BrxReadsJob()
+        s.n_align, s.d_text, s.n_text = n_align, up(text), int(text.numel())
+        s.d_seq_src, s.d_qual_src = up(np.ascontiguousarray(seq_src, dtype=np.uint64)), up(np.ascontiguousarray(qual_src, dtype=np.uint64))
+        s.d_align_read_off = up(np.ascontiguousarray(read_off, dtype=np.uint64))
+        s.d_seq, s.d_qual, s.d_flags = seq.data_ptr(), qual.data_ptr(), flags.data_ptr()
+        self._check(self.lib.brx_reads_pack(self.ctx, ctypes.byref(s), self._stream()))
+        return seq, qual
+
+    def reads_last(self):
+        """ms of the last fastq_scan and the last reads_pack under set_kernel_timing."""
+        ms = (ctypes.c_float * 2)()
+        self._check(self.lib.brx_reads_last(self.ctx, ctypes.byref(ms)))
         return dict(zip(('scan', 'pack'), [float(x) for x in ms]))
 
     def window_last(self):

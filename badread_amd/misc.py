@@ -116,7 +116,7 @@ def load_fastq(filename, output=sys.stderr, dot_interval=1000):
                 continue
             body = [next(rows, None) for _ in range(3)]
             if body[2] is None:
-                raise EOFError('{}: the last record is cut short'.format(filename))
+                raise StopIteration('{}: the last record is cut short'.format(filename))     # the reference's type: its next() ran dry
             reads[head[1:].split()[0].decode()] = (body[0].strip().upper().decode(), body[2].strip().decode())
             records += 1
             if records % dot_interval == 0:

@@ -13,6 +13,8 @@ window recorded per key.
 
 With --gpu-loader (README: The device loader) the PAF is parsed by brx_paf_scan (alignment.load_alignments_device) and the part arrays and
 reference slices are written by brx_align_pack (Job.packed); the host then only joins the read slices.  Same text, same exits.
+With --gpu-reads on top (README: The device read loader) the FASTQ is parsed by brx_fastq_scan (reads.load_fastq_device) and stays on
+the device, and the read slices are cut out of it by brx_reads_pack: no join either.
 """
 import collections
 import itertools
@@ -23,6 +25,7 @@ import numpy as np
 
 from .alignment import DeviceAlignments, load_alignments, load_alignments_device
 from .misc import _COMPLEMENT, float_to_str, load_fasta, load_fastq, only_acgt, reverse_complement
+from .reads import DeviceReads, load_fastq_device
 
 _TYPE = {'M': 0, 'I': 1, 'D': 2}
 EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -82,28 +85,40 @@ class Job(object):
         """The same job for packed[first:end] of a DeviceAlignments (--gpu-loader): seq and qual joined here as above, the part arrays
         and ref written on the device by brx_align_pack from the CIGAR text that already lies there -- tensors, which model_count and
         window_means take as they are.  The checks read the scan records (sum_m / sum_i / sum_d) instead of walking parts; slices is
-        made per alignment when a spill path asks for one."""
+        made per alignment when a spill path asks for one.  With a DeviceReads (--gpu-reads) seq and qual are tensors too: the host
+        only says where every slice lies in the FASTQ text (Python's clipping rule on the record's lengths) and brx_reads_pack copies."""
         self = cls.__new__(cls)
+        on_device = isinstance(reads, DeviceReads)
         alignments, rec = list.__getitem__(packed, slice(first, end)), packed.rec[first:end]
         reftext, ref_at = _device_reference(engine, refs, packed)
         n = len(alignments)
         seqs, quals = [], []
-        read_len, ref_off, ref_len = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+        read_len, ref_off, ref_len, seq_src, qual_src = (np.zeros(n, dtype=np.uint64) for _ in range(5))
         used_read, used_ref = (rec['sum_m'] + rec['sum_i']).tolist(), (rec['sum_m'] + rec['sum_d']).tolist()
         for k, a in enumerate(alignments):
             check_alignment_matches_read_and_refs(a, reads, refs)
-            read_seq, read_qual = (x[a.read_start:a.read_end] for x in reads[a.read_name])
+            if on_device:                                   # ranges stand in for the two strings: only their lengths are asked for
+                seq_at, seq_n, qual_at, qual_n = reads.spans(a.read_name)
+                read_seq = range(*slice(a.read_start, a.read_end).indices(seq_n))
+                read_qual = range(*slice(a.read_start, a.read_end).indices(qual_n))
+                seq_src[k], qual_src[k] = seq_at + read_seq.start, qual_at + read_qual.start
+            else:
+                read_seq, read_qual = (x[a.read_start:a.read_end] for x in reads[a.read_name])
             lo, hi, _ = slice(a.ref_start, a.ref_end).indices(len(refs[a.ref_name]))           # Python's clipping rule
             if used_read[k] > len(read_seq) or used_ref[k] > max(hi - lo, 0) or len(read_qual) < len(read_seq):
                 sys.exit(f'Error: the CIGAR of {a!r} runs past its read or reference range')
-            seqs.append(read_seq); quals.append(read_qual[:len(read_seq)])
+            if not on_device:
+                seqs.append(read_seq); quals.append(read_qual[:len(read_seq)])
             read_len[k], ref_off[k], ref_len[k] = len(read_seq), ref_at[a.ref_name] + lo, max(hi - lo, 0)
-        enc = lambda parts_: np.frombuffer(''.join(parts_).encode('latin-1') or b'\0', dtype=np.uint8)
-        self.seq, self.qual = enc(seqs), enc(quals)
         offsets = lambda x: np.concatenate((np.zeros(1, dtype=np.uint64), np.cumsum(x, dtype=np.uint64)))
         self.align_part_off = offsets(rec['n_parts'])
         self.align_col_off = offsets(rec['sum_m'] + rec['sum_i'] + rec['sum_d'])
         self.align_read_off = offsets(read_len)
+        if on_device:
+            self.seq, self.qual = engine.reads_pack(reads.text, seq_src, qual_src, self.align_read_off)
+        else:
+            enc = lambda parts_: np.frombuffer(''.join(parts_).encode('latin-1') or b'\0', dtype=np.uint8)
+            self.seq, self.qual = enc(seqs), enc(quals)
         self.align_ref_off = offsets(ref_len)
         from .engine import PACK_ALIGN_DTYPE
         desc = np.zeros(n, dtype=PACK_ALIGN_DTYPE)
@@ -197,6 +212,19 @@ def _engine(args, engine):
     return engine
 
 
+def check_gpu_reads(args):
+    if getattr(args, 'gpu_reads', False) and not getattr(args, 'gpu_loader', False):
+        sys.exit('Error: --gpu-reads needs --gpu-loader')
+
+
+def _reads(args, engine, output):
+    """(the reads of a model command, the engine): load_fastq, or with --gpu-reads its device twin, which needs the engine first."""
+    if getattr(args, 'gpu_reads', False):
+        engine = _engine(args, engine)
+        return load_fastq_device(args.reads, engine, output=output), engine
+    return load_fastq(args.reads, output=output), engine
+
+
 def _table(engine, kind, job, k, max_del, n_ksizes, first_bits=16):
     """The counted table of a job.  The first table has 2^first_bits slots, raised to four times the keys the job is expected to hold;
     a first_bits below the default is taken as it is, so the growth below is what finds the size."""
@@ -248,8 +276,9 @@ def count_error_model(engine, job, k, first_bits=16):
 
 def make_error_model(args, output=sys.stderr, dot_interval=1000, engine=None, stdout=None):
     stdout = stdout or sys.stdout
+    check_gpu_reads(args)
     refs, _, _, _, _ = load_fasta(args.reference)
-    reads = load_fastq(args.reads, output=output)
+    reads, engine = _reads(args, engine, output)
     engine = _engine(args, engine)
     alignments = _load(args, engine, output)
     if len(alignments) == 0:
@@ -331,8 +360,9 @@ def count_qscore_model(engine, job, k_size, max_del, first_bits=16):
 
 def make_qscore_model(args, output=sys.stderr, dot_interval=1000, engine=None, stdout=None):
     stdout = stdout or sys.stdout
+    check_gpu_reads(args)
     refs, _, _, _, _ = load_fasta(args.reference)
-    reads = load_fastq(args.reads, output=output)
+    reads, engine = _reads(args, engine, output)
     engine = _engine(args, engine)
     alignments = _load(args, engine, output)
     if len(alignments) == 0:

@@ -15,7 +15,8 @@ The doubles are made from those here with the reference's own expressions, so th
 
 Additive: --summary PATH (one TSV line per alignment, no window values leave the device), --save DIR (one PNG per alignment) and
 --max_alignments N.  Drawing needs matplotlib, which is imported only where a plot is drawn.  --gpu-loader: the PAF parsed and every
-chunk packed on the device (alignment.load_alignments_device, model_builder.Job.packed), the same output.
+chunk packed on the device (alignment.load_alignments_device, model_builder.Job.packed), the same output.  --gpu-reads on top of it: the
+FASTQ parsed on the device too and the read slices cut out of it there (reads.load_fastq_device).
 """
 import contextlib
 import itertools
@@ -27,7 +28,9 @@ import numpy as np
 
 from .alignment import NO_D, DeviceAlignments, load_alignments, load_alignments_device
 from .misc import load_fasta, load_fastq
-from .model_builder import Job, check_alignment_matches_read_and_refs
+from .model_builder import Job, check_alignment_matches_read_and_refs, check_gpu_reads
+from .reads import load_fastq_device
+from .reads import read_length as read_length_of
 
 PLOT_CHUNK_BASES = 1 << 26                 # read bases per device call: 20 bytes of scratch each, 28 with --qual
 SUMMARY_COLUMNS = ('read_name', 'read_length', 'read_start', 'read_end', 'strand', 'ref_name', 'ref_start', 'ref_end',
@@ -78,7 +81,7 @@ def _check_packed(a, rec, reads, refs, qual):
     it: the D with the most read bases in front of it is the last one in file order for '+' and, the list being read backwards, the
     first one for '-'."""
     check_alignment_matches_read_and_refs(a, reads, refs)
-    length = len(range(*slice(a.read_start, a.read_end).indices(len(reads[a.read_name][0]))))
+    length = len(range(*slice(a.read_start, a.read_end).indices(read_length_of(reads, a.read_name))))
     first_d, last_d, used_read = int(rec['first_d']), int(rec['last_d']), int(rec['sum_m']) + int(rec['sum_i'])
     if first_d != NO_D and (used_read - first_d >= length if a.strand == '-' else last_d >= length):
         sys.exit(f'Error: the CIGAR of {a!r} ends in a deletion with no read base after it')
@@ -179,7 +182,14 @@ def plot_window_identity(args, output=sys.stdout, engine=None, stdout=None):
         sys.exit('Error: --window must be at least 1')
     if summary is not None and not pathlib.Path(summary).resolve().parent.is_dir():
         sys.exit(f'Error: the directory of --summary {summary} does not exist')
-    reads = load_fastq(args.reads, output=output)
+    check_gpu_reads(args)
+    if getattr(args, 'gpu_reads', False):
+        if engine is None:
+            from .engine import default_engine
+            engine = default_engine()
+        reads = load_fastq_device(args.reads, engine, output=output)
+    else:
+        reads = load_fastq(args.reads, output=output)
     refs, _, _, _, _ = load_fasta(args.reference)
     if getattr(args, 'gpu_loader', False):
         if engine is None:
@@ -202,7 +212,7 @@ def plot_window_identity(args, output=sys.stdout, engine=None, stdout=None):
         results = window_means(engine, refs, reads, alignments, window, qual, values=draw, lengths=lengths)
         for index, (a, (stat, err_sum, qual_sum)) in enumerate(zip(alignments, results)):
             print(a, file=stdout)
-            read_length = len(reads[a.read_name][0])
+            read_length = read_length_of(reads, a.read_name)
             if summary is not None:
                 table.write(summary_line(a, read_length, stat, window, qual) + '\n')
             if draw:

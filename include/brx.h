@@ -445,6 +445,61 @@ int brx_align_pack(brx_ctx *ctx, const brx_pack_job *job, void *hip_stream);
 /* ms between HIP events of the last brx_paf_scan and brx_align_pack on ctx that ran under brx_set_kernel_timing */
 int brx_loader_last(const brx_ctx *ctx, float ms[2]);
 
+/* ------------------------------------------------------------- the device read loader (README: The device read loader (`--gpu-reads`))
+ * What load_fastq does per byte and what model_builder.Job does per read base, on the device.
+ *
+ * brx_fastq_scan: n_bytes of FASTQ text in device memory -> one brx_fastq_rec per record, for files of the REGULAR LAYOUT.  The rule is
+ * the reference's load_fastq: lines end at '\n' only; a line whose stripped form begins with '@' opens a record and the next three lines
+ * belong to it whatever they hold; strip() and split() take the six ASCII blanks (space, \t, \n, \r, \x0b, \x0c), so a CRLF file is an
+ * ordinary file.  The layout is regular when that rule provably finds its headers on the lines 0, 4, 8, ...: the number of lines is a
+ * multiple of 4 (a last line without '\n' is a line, the empty piece behind a final '\n' is not), every line 4k, stripped, begins with
+ * '@' and has a name behind it (stripped[1:].split() is not empty), and no byte is 0x80 or more.  Any other file sets a bit in *layout,
+ * *n_recs is 0, what d_recs holds is not promised, and the call still returns BRX_OK: the host loads such a file.
+ *   BRX_FQ_LINES    the line count is not a multiple of 4 (nothing else of the file is looked at, the other bits stay 0)
+ *   BRX_FQ_HEADER   some line 4k opens no record, or is a bare '@'
+ *   BRX_FQ_HIGH     a byte of 0x80 or more
+ * A record: head_off = the first byte of the header line; the name at head_off + name_off, name_len bytes; seq_off / seq_len and qual_off
+ * / qual_len = the second and the fourth line without the blanks at both ends (absolute offsets; a line of blanks alone has length 0 and
+ * its offset is where the line ends); flags = 0; reserved = 0.
+ * d_scratch: brx_fastq_scan_scratch(n_bytes) bytes of device memory -- 8 bytes per 16 bytes of text for the scan and 8 bytes per line for
+ * up to one line per 64 bytes of text.  A file with more lines than that needs more: BRX_E_SCRATCH names the size, as for any scratch
+ * that is too small.
+ *   BRX_E_ARG                            NULL n_recs, layout or d_text; 2^42 bytes or more; 2^31 records or more; a line of 2^32 bytes
+ *   BRX_E_SCRATCH + brx_scratch_needed() scratch_bytes is too small
+ *   BRX_E_OUTPUT + brx_output_needed()   rec_cap is below the number of records, or d_recs is NULL (needed: the records); nothing written
+ * Zero bytes is a valid call (no record, layout 0).  Synchronous on `hip_stream`; takes nothing from the simulate pipeline's state.      */
+#define BRX_FQ_LINES 1u
+#define BRX_FQ_HEADER 2u
+#define BRX_FQ_HIGH 4u
+typedef struct {
+    uint64_t head_off;
+    uint32_t name_off, name_len;
+    uint64_t seq_off, qual_off;
+    uint32_t seq_len, qual_len;
+    uint32_t flags, reserved;
+} brx_fastq_rec;
+size_t brx_fastq_scan_scratch(uint64_t n_bytes);
+int brx_fastq_scan(brx_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, brx_fastq_rec *d_recs, uint64_t rec_cap, uint64_t *n_recs,
+                   uint32_t *layout, void *d_scratch, size_t scratch_bytes, void *hip_stream);
+
+/* brx_reads_pack: seq and qual of model_builder.Job from the FASTQ text that lies on the device.  For alignment k with
+ * len = d_align_read_off[k + 1] - d_align_read_off[k]:  d_seq[off[k] + i] = upper(d_text[d_seq_src[k] + i]) (only a-z change, as
+ * bytes.upper()) and d_qual[off[k] + i] = d_text[d_qual_src[k] + i], i < len.  d_seq and d_qual hold off[n_align] bytes; every byte of
+ * them is written once and none needs to be preset.  An alignment of no bases is valid; so are zero alignments.
+ *   BRX_E_ARG   a NULL array that is needed; offsets that do not begin at 0 or do not ascend, a source range that leaves
+ *               [0, n_text): d_flags[0] is then 1 and nothing was read or written, out of range or in it
+ * No global atomics, no waiting between workgroups.  Synchronous on `hip_stream`.                                                       */
+typedef struct {
+    uint32_t n_align, reserved;
+    const uint8_t *d_text; uint64_t n_text;
+    const uint64_t *d_seq_src, *d_qual_src, *d_align_read_off;   /* n_align, n_align, n_align + 1 */
+    uint8_t *d_seq, *d_qual;
+    uint32_t *d_flags;                 /* [1], preset to 0: set where the job is refused */
+} brx_reads_job;
+int brx_reads_pack(brx_ctx *ctx, const brx_reads_job *job, void *hip_stream);
+/* ms between HIP events of the last brx_fastq_scan and brx_reads_pack on ctx that ran under brx_set_kernel_timing */
+int brx_reads_last(const brx_ctx *ctx, float ms[2]);
+
 /* ---- output stage: the FASTQ bytes of a batch as gzip members, made on the device ----
  * Replaces the `| gzip` the reference's users put behind /root/reference/badread/simulate.py:73-82 (print of the
  * record text).  d_in: n_bytes of text in device memory.  d_block_off: n_blocks + 1 ascending byte offsets (device
