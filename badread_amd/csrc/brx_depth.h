@@ -1,6 +1,6 @@
 /*
  * brx_depth.h -- the true coverage of the reference (--truth-depth): the end points of a batch's truth records (brx_emit_depth) and, at
- * the end of the job, the bedGraph text of all of them (brx_depth_bedgraph).  Included once by brx_hip.hip after brx_paf.h.
+ * the end of the job, the bedGraph text of all of them (brx_depth_bedgraph).  A sink of the record walk of brx_paf.h.
  *
  * Per batch.  DepthSink is a fourth sink of the record walk of brx_paf.h (paf_read): of every record it keeps the contig, tstart and tend
  * and nothing else -- one sweep over the record's columns counts the target bases (= X D), which with the origin of the first column
@@ -23,15 +23,14 @@
  *      differs from the depth after the group before; k_dp_points compacts those.
  *   3. Text (the scan over DpSrcLine, k_dp_lines).  A change point below the contig's length owns the line up to the next change point
  *      -- which belongs to the same contig, as the contig's length is one -- sized with paf_digits, placed by the scan.
- * Every scan is the same three kernels over a functor (dp_scan in brx_hip.hip): k_dp_reduce (a sum per tile), k_dp_scan_sums (one
- * workgroup over the tile sums), k_dp_apply (the tile's own scan on top of its sum).  Order between workgroups comes from kernel
- * boundaries alone; no workgroup waits for another and global memory takes no atomics.
+ * Every scan is dp_scan of brx_scan.h over one of the functors below.
  */
 #ifndef BRX_DEPTH_H
 #define BRX_DEPTH_H
 
-#define BRX_DP_THREADS 256u
-#define BRX_DP_ITEMS (BRX_DEPTH_TILE / BRX_DP_THREADS)
+#include "brx_scan.h"
+#include "brx_paf.h"
+
 #define BRX_DP_POS_MASK ((1ull << 39) - 1ull)
 
 /* ---- per batch: the end points of the truth records ------------------------------------------------------------------------------ */
@@ -75,73 +74,7 @@ __global__ void __launch_bounds__(64) k_depth_write(BrxDev d, const RS *rs, cons
     paf_read(w, d, s, r, segs, arena, R);
 }
 
-/* ---- the scans ------------------------------------------------------------------------------------------------------------------- */
-__device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t v) {
-    const int lane = lane_id();
-#pragma unroll
-    for (int dd = 1; dd < 64; dd <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, dd, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), dd, 64);
-        if (lane >= dd) v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
-}
-/* Inclusive scan of v over the workgroup's threads in thread order; *total = the workgroup's sum.  lds: a word per wave.  Every thread
-   calls it. */
-__device__ __forceinline__ uint64_t dp_block_scan(uint64_t v, uint64_t *lds, uint64_t *total) {
-    const uint32_t w = threadIdx.x >> 6;
-    const uint64_t inc = wave_incl_scan_u64(v);
-    __syncthreads();                                   /* the words of the call before have been read */
-    if (lane_id() == 63) lds[w] = inc;
-    __syncthreads();
-    uint64_t base = 0, tot = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < BRX_DP_THREADS / 64u; ++x) { const uint64_t s = lds[x]; if (x < w) base += s; tot += s; }
-    *total = tot;
-    return base + inc;
-}
-
-/* sums[tile] = the sum of src over the tile; a thread takes BRX_DP_ITEMS consecutive elements */
-template <class Src>
-__global__ void __launch_bounds__(BRX_DP_THREADS) k_dp_reduce(Src src, uint64_t n, uint64_t *sums) {
-    __shared__ uint64_t lds[BRX_DP_THREADS / 64u];
-    const uint64_t i0 = (uint64_t)blockIdx.x * BRX_DEPTH_TILE + (uint64_t)threadIdx.x * BRX_DP_ITEMS;
-    uint64_t v = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < BRX_DP_ITEMS; ++x) if (i0 + x < n) v += src(i0 + x);
-    uint64_t tot;
-    dp_block_scan(v, lds, &tot);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-/* the tile sums to what lies before each tile, in place; sums[n_tiles] = the total.  One workgroup. */
-__global__ void __launch_bounds__(BRX_DP_THREADS) k_dp_scan_sums(uint64_t *sums, uint32_t n_tiles) {
-    __shared__ uint64_t lds[BRX_DP_THREADS / 64u];
-    uint64_t run = 0;
-    for (uint32_t b = 0; b < n_tiles; b += BRX_DP_THREADS) {
-        const uint32_t i = b + threadIdx.x;
-        const uint64_t v = i < n_tiles ? sums[i] : 0u;
-        uint64_t tot;
-        const uint64_t inc = dp_block_scan(v, lds, &tot);
-        if (i < n_tiles) sums[i] = run + inc - v;
-        run += tot;
-    }
-    if (threadIdx.x == 0) sums[n_tiles] = run;
-}
-/* out[i] = the sum of src over [0, i] */
-template <class Src>
-__global__ void __launch_bounds__(BRX_DP_THREADS) k_dp_apply(Src src, uint64_t n, const uint64_t *sums, uint64_t *out) {
-    __shared__ uint64_t lds[BRX_DP_THREADS / 64u];
-    const uint64_t i0 = (uint64_t)blockIdx.x * BRX_DEPTH_TILE + (uint64_t)threadIdx.x * BRX_DP_ITEMS;
-    uint64_t val[BRX_DP_ITEMS], v = 0;
-#pragma unroll
-    for (uint32_t x = 0; x < BRX_DP_ITEMS; ++x) { val[x] = i0 + x < n ? src(i0 + x) : 0u; v += val[x]; }
-    uint64_t tot;
-    uint64_t run = sums[blockIdx.x] + dp_block_scan(v, lds, &tot) - v;
-#pragma unroll
-    for (uint32_t x = 0; x < BRX_DP_ITEMS; ++x) { run += val[x]; if (i0 + x < n) out[i0 + x] = run; }
-}
-
 /* ---- what the scans run over ------------------------------------------------------------------------------------------------------ */
-struct DpSrcTable { const uint32_t *t; __device__ uint64_t operator()(uint64_t i) const { return t[i]; } };
 /* the sorted keys: low word delta + 1, high word "ends its group" */
 struct DpSrcPack {
     const uint64_t *k; uint64_t n;

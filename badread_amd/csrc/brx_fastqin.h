@@ -1,12 +1,12 @@
 /*
  * brx_fastqin.h -- the FASTQ that `error_model`, `qscore_model` and `plot` read, parsed on the device, and the read slices of a job packed
- * there (--gpu-reads; README: The device read loader).  Included once by brx_hip.hip after brx_pafin.h; the scan is that of brx_depth.h.
+ * there (--gpu-reads; README: The device read loader).  The scan is that of brx_scan.h.
  *   load_fastq    /root/reference/badread/misc.py:97-119   (a stripped line that begins with '@' opens a record of four lines)
  *   Job.__init__  badread_amd/model_builder.py            (seq: the read slices upper-cased, qual: their qualities, back to back)
  * brx_fastq_scan: text -> one brx_fastq_rec per four lines, for the layout in which the reference's state machine finds its headers on the
  * lines 0, 4, 8, ...: the line count a multiple of 4, every line 4k a header with a name, no byte of 0x80 or more.  Anything else is
  * named in *layout and the host loads the file.
- *   1. the scan of brx_depth.h over FqSrcStarts16: an element is a group of 16 text bytes, its value the line starts among them (byte 0
+ *   1. the scan of brx_scan.h over FqSrcStarts16: an element is a group of 16 text bytes, its value the line starts among them (byte 0
  *      and every byte behind a '\n').  8 bytes of prefix per 16 bytes of text.  k_fq_starts, a thread per group, writes the offset of
  *      each of its line starts to line_start[] and n_bytes behind the last; a byte of 0x80 or more raises BRX_FQ_HIGH.
  *   2. k_fq_records, a thread per record: the four line starts and the next one, the header, sequence and quality lines stripped of the
@@ -19,6 +19,8 @@
  */
 #ifndef BRX_FASTQIN_H
 #define BRX_FASTQIN_H
+
+#include "brx_scan.h"
 
 #define BRX_FQ_THREADS 256u
 #define BRX_FQ_TILE (BRX_FQ_THREADS * 16u)              /* output bytes of a workgroup of k_fq_pack */

@@ -23,13 +23,6 @@
 
 #include "brx_kernels.h"
 #include "brx_finplan.h"
-#include "brx_paf.h"
-#include "brx_sam.h"
-#include "brx_bam.h"
-#include "brx_depth.h"
-#include "brx_window.h"
-#include "brx_pafin.h"
-#include "brx_fastqin.h"
 
 #define BRX_KEV_MAX 2048
 
@@ -350,7 +343,9 @@ struct KTimer {
     }
     ~KTimer() { if (slot >= 0) (void)hipEventRecord(c->kev_e[slot], st); }
 };
-#define KTIMED(kind, stream) KTimer ktimer_##__LINE__(c, (kind), (stream))
+#define BRX_PASTE_(a, b) a##b
+#define BRX_PASTE(a, b) BRX_PASTE_(a, b)
+#define KTIMED(kind, stream) KTimer BRX_PASTE(ktimer_, __LINE__)(c, (kind), (stream))
 
 extern "C" uint32_t brx_last_mutate_passes(const brx_ctx *c) { return c ? c->mutate_passes : 0; }
 extern "C" uint32_t brx_last_final_launches(const brx_ctx *c) { return c ? c->final_launches : 0; }
@@ -388,16 +383,20 @@ static int to_device(brx_ctx *c, hipStream_t st, void *d_dst, const void *h_src,
     hipLaunchKernelGGL(k_copy_words, dim3((unsigned)std::min<size_t>((n + 255) / 256, 128)), dim3(64), 0, st, (uint32_t *)d_dst, (const uint32_t *)alias, n);
     return BRX_OK;
 }
-/* the staging block holds at least `bytes` (grown between batches only: nothing of the context is in flight) */
+/* (*h, *d) becomes a fresh pinned block of `want` bytes and its device view; what it held is gone.  The callers decide when to grow and
+   by how much; nothing of the context may be in flight. */
+static int pinned_regrow(brx_ctx *c, uint8_t **h, uint8_t **d, size_t *have, size_t want) {
+    if (*h) { (void)hipHostFree(*h); *h = nullptr; *d = nullptr; *have = 0; }
+    HIPCHK(c, hipHostMalloc((void **)h, want, hipHostMallocMapped));
+    void *dp = nullptr;
+    HIPCHK(c, hipHostGetDevicePointer(&dp, *h, 0));
+    *d = (uint8_t *)dp; *have = want;
+    return BRX_OK;
+}
+/* the staging block holds at least `bytes` (grown between batches only), in whole megabytes */
 static int stage_reserve(brx_ctx *c, size_t bytes) {
     if (c->stage_bytes >= bytes) return BRX_OK;
-    if (c->h_stage) { (void)hipHostFree(c->h_stage); c->h_stage = nullptr; c->d_stage = nullptr; c->stage_bytes = 0; }
-    bytes = (bytes + ((size_t)1 << 20)) & ~(((size_t)1 << 20) - 1);
-    HIPCHK(c, hipHostMalloc((void **)&c->h_stage, bytes, hipHostMallocMapped));
-    void *dp = nullptr;
-    HIPCHK(c, hipHostGetDevicePointer(&dp, c->h_stage, 0));
-    c->d_stage = (uint8_t *)dp; c->stage_bytes = bytes;
-    return BRX_OK;
+    return pinned_regrow(c, &c->h_stage, &c->d_stage, &c->stage_bytes, (bytes + ((size_t)1 << 20)) & ~(((size_t)1 << 20) - 1));
 }
 
 static int read_totals(brx_ctx *c, hipStream_t st, const uint64_t *d_totals, int n) {
@@ -1193,587 +1192,5 @@ extern "C" int brx_align_batch(brx_ctx *c, uint32_t n_pairs, const uint8_t *d_qu
     return BRX_OK;
 }
 
-/* f4: the counting loops of the model builders (brx_model.h).  The job struct of the ABI has the layout of BrxMbJob. */
-static_assert(sizeof(brx_model_job) == sizeof(BrxMbJob), "brx_model_job and BrxMbJob must have the same layout");
-extern "C" int brx_model_count(brx_ctx *c, int kind, const brx_model_job *job, void *hip_stream) {
-    if (!c || !job || (kind != 0 && kind != 1)) return BRX_E_ARG;
-    c->paf_valid = false;
-    if (job->n_align == 0 || job->n_cols == 0) return BRX_OK;
-    if (kind == 0 && (job->k < 2 || 2 * job->k + 5 + 2 * BRX_MB_MAX_READ_KMER > 64)) return fail(c, BRX_E_ARG, "error model k-mer size %u not supported (2..8)", job->k);
-    if (kind == 1 && (job->n_ksizes < 1 || job->n_ksizes > 16 || job->max_del > 15)) return fail(c, BRX_E_ARG, "qscore model: k_size up to 31, max_del up to 15");
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    BrxMbJob j;
-    memcpy(&j, job, sizeof(j));
-    const uint64_t nb = (job->n_cols + 255) / 256;
-    hipLaunchKernelGGL(k_mb_expand, dim3((unsigned)nb), dim3(256), 0, st, j);
-    if (kind == 0) hipLaunchKernelGGL(k_mb_error, dim3((unsigned)nb), dim3(256), 0, st, j);
-    else hipLaunchKernelGGL(k_mb_qscore, dim3((unsigned)((job->n_cols * job->n_ksizes + 255) / 256)), dim3(256), 0, st, j);
-    uint32_t flags[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(flags, job->d_flags, sizeof(flags), hipMemcpyDeviceToHost, st));
-    { int rcw = wait_stream(c, st, "model builder"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    if (flags[0] & 1u) return fail(c, BRX_E_OUTPUT, "model builder: hash table full");
-    return BRX_OK;
-}
-
-/* f2: gzip members on the device (brx_gzip_dev.h) */
-static BrxGzConst gz_const() {
-    BrxGzConst K;
-    K.x2n[0] = 0x40000000u;
-    for (int i = 1; i < 32; ++i) K.x2n[i] = brx_gz_mulmod(K.x2n[i - 1], K.x2n[i - 1]);
-    return K;
-}
-extern "C" size_t brx_gzip_device_bound(size_t n_bytes, uint32_t n_blocks) {
-    if (!n_bytes) return 8;
-    const size_t nb = n_blocks ? n_blocks : (n_bytes + BRX_GZ_BLOCK - 1) / BRX_GZ_BLOCK;
-    return nb * (size_t)brx_gz_member_bound(0) + (15 * n_bytes + 7) / 8 + nb + 16;      /* sum over the blocks of brx_gz_member_bound(len) */
-}
-extern "C" size_t brx_gzip_device_scratch(size_t n_bytes, uint32_t n_blocks) {
-    const size_t nb = n_blocks ? n_blocks : (n_bytes + BRX_GZ_BLOCK - 1) / BRX_GZ_BLOCK;
-    return nb * (size_t)(4 * BRX_GZ_TAB + 4 * BRX_GZ_OFFS + 8) + (nb + 1) * 8 + 1024;
-}
-/* gzip members (brx_gzip_device) or BGZF blocks (brx_bgzf_device: fixed blocks of BRX_BGZF_BLOCK bytes) of d_in */
-template <bool BGZF>
-static int gz_members(brx_ctx *c, const void *d_in, size_t n_bytes, const uint64_t *d_block_off, uint32_t n_blocks, void *d_out, size_t out_cap,
-                      void *d_scratch, size_t scratch_bytes, size_t *out_bytes, void *hip_stream) {
-    if (!c || !out_bytes || (n_bytes && (!d_in || !d_out || !d_scratch)) || (d_block_off && !n_blocks)) return BRX_E_ARG;
-    *out_bytes = 0;
-    if (!n_bytes) return BRX_OK;
-    if ((uintptr_t)d_out & 3u) return fail(c, BRX_E_ARG, "brx_gzip_device: the output buffer must be 4-byte aligned");
-    const uint32_t nb = d_block_off ? n_blocks : (uint32_t)((n_bytes + BrxGzFlavour<BGZF>::block - 1) / BrxGzFlavour<BGZF>::block);
-    if (scratch_bytes < brx_gzip_device_scratch(n_bytes, nb)) return fail(c, BRX_E_SCRATCH, "brx_gzip_device: scratch too small (%zu < %zu)", scratch_bytes, brx_gzip_device_scratch(n_bytes, nb));
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    static const BrxGzConst K = gz_const();
-    uint8_t *p = (uint8_t *)d_scratch;
-    uint64_t *member_off = (uint64_t *)p; p += ((size_t)nb + 1) * 8;
-    uint32_t *tabs = (uint32_t *)p; p += (size_t)nb * 4 * BRX_GZ_TAB;
-    uint32_t *offs = (uint32_t *)p; p += (size_t)nb * 4 * BRX_GZ_OFFS;
-    uint32_t *crcs = (uint32_t *)p; p += (size_t)nb * 4;
-    uint32_t *sizes = (uint32_t *)p;
-    const uint32_t grid = std::min<uint32_t>(nb, (uint32_t)c->n_cu * 8u);
-    hipLaunchKernelGGL((k_gz_plan<BGZF>), dim3(grid), dim3(64), 0, st, (const uint8_t *)d_in, (uint64_t)n_bytes, d_block_off, nb, K, tabs, offs, crcs, sizes);
-    hipLaunchKernelGGL(k_gz_scan, dim3(1), dim3(64), 0, st, nb, sizes, member_off);
-    uint64_t total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, member_off + nb, 8, hipMemcpyDeviceToHost, st));
-    { int rcw = wait_stream(c, st, "brx_gzip_device (plan)"); if (rcw) return rcw; }
-    if (total + 8 > out_cap) { c->output_needed = (size_t)total + 8; return fail(c, BRX_E_OUTPUT, "brx_gzip_device: output buffer too small: need %llu bytes", (unsigned long long)total + 8); }
-    HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)((total + 7) & ~(uint64_t)3), st));
-    hipLaunchKernelGGL((k_gz_pack<BGZF>), dim3(grid), dim3(64), 0, st, (const uint8_t *)d_in, (uint64_t)n_bytes, d_block_off, nb, (uint8_t *)d_out, member_off, tabs, offs, crcs);
-    { int rcw = wait_stream(c, st, "brx_gzip_device (pack)"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    *out_bytes = (size_t)total;
-    return BRX_OK;
-}
-extern "C" int brx_gzip_device(brx_ctx *c, const void *d_in, size_t n_bytes, const uint64_t *d_block_off, uint32_t n_blocks, void *d_out, size_t out_cap,
-                               void *d_scratch, size_t scratch_bytes, size_t *out_bytes, void *hip_stream) {
-    return gz_members<false>(c, d_in, n_bytes, d_block_off, n_blocks, d_out, out_cap, d_scratch, scratch_bytes, out_bytes, hip_stream);
-}
-static uint32_t bgzf_blocks(size_t n_bytes) { return (uint32_t)((n_bytes + BRX_BGZF_BLOCK - 1) / BRX_BGZF_BLOCK); }
-extern "C" size_t brx_bgzf_device_bound(size_t n_bytes) {
-    const size_t nb = bgzf_blocks(n_bytes);
-    return nb * (18 + (BRX_GZ_HDR_BITS + 15 + 7) / 8 + 8) + (15 * n_bytes + 7) / 8 + nb + 16;
-}
-extern "C" size_t brx_bgzf_device_scratch(size_t n_bytes) { return brx_gzip_device_scratch(n_bytes, bgzf_blocks(n_bytes)); }
-extern "C" int brx_bgzf_device(brx_ctx *c, const void *d_in, size_t n_bytes, void *d_out, size_t out_cap, void *d_scratch, size_t scratch_bytes,
-                               size_t *out_bytes, void *hip_stream) {
-    if (n_bytes > (size_t)BRX_BGZF_BLOCK * 0xFFFFFFFFull) return c ? fail(c, BRX_E_ARG, "brx_bgzf_device: input too long") : BRX_E_ARG;
-    return gz_members<true>(c, d_in, n_bytes, nullptr, 0, d_out, out_cap, d_scratch, scratch_bytes, out_bytes, hip_stream);
-}
-
-/* ---- truth alignments of the last simulate batch: PAF text (brx_paf.h), SAM records (brx_sam.h) or BAM records (brx_bam.h) ---- */
-enum { TRUTH_PAF = 0, TRUTH_SAM = 1, TRUTH_BAM = 2, TRUTH_DEPTH = 3 };
-/* f(std::integral_constant<uint32_t, TAGS>, std::bool_constant<F>) for the tags and "some format bit" of a call: one instantiation of the SAM /
-   BAM kernels per pair.  TAGS = 0 is the untagged code, nothing of the tags in its column loops; F = false the code of brx_emit_*_tags,
-   nothing of the formats in it; with F the bits are a value of the grid's. */
-template <class Fn> static void with_tags_fmt(uint32_t tags, bool fmtd, Fn f) {
-    auto with_fmt = [&](auto T) { if (fmtd) f(T, std::true_type{}); else f(T, std::false_type{}); };
-    switch (tags) {
-        case 0: with_fmt(std::integral_constant<uint32_t, 0u>{}); break;
-        case 1: with_fmt(std::integral_constant<uint32_t, 1u>{}); break;
-        case 2: with_fmt(std::integral_constant<uint32_t, 2u>{}); break;
-        default: with_fmt(std::integral_constant<uint32_t, 3u>{}); break;
-    }
-}
-static int emit_truth(brx_ctx *c, int kind, uint32_t fmt, uint32_t tags, uint32_t max_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    if (!c || !out_bytes) return BRX_E_ARG;
-    *out_bytes = 0;
-    if (tags & ~(uint32_t)(BRX_TAG_MD | BRX_TAG_SA)) return fail(c, BRX_E_ARG, "truth tags %#x: only BRX_TAG_MD | BRX_TAG_SA", tags);
-    if ((fmt & ~(uint32_t)(BRX_FMT_EQX | BRX_FMT_CS | BRX_FMT_CS_LONG)) || (fmt & (BRX_FMT_CS | BRX_FMT_CS_LONG)) == BRX_FMT_CS_LONG)
-        return fail(c, BRX_E_ARG, "truth format %#x: BRX_FMT_EQX | BRX_FMT_CS | BRX_FMT_CS_LONG, the last only with BRX_FMT_CS", fmt);
-    if (!c->paf_valid) return fail(c, BRX_E_STATE, "no simulate batch on this context to emit truth alignments for");
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    const uint32_t n = c->paf_reads;
-    auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
-    const size_t len_at = 0, best_at = pad((size_t)n * 4), off_at = best_at + pad((size_t)n * 4);
-    const size_t nrec_at = off_at + pad(((size_t)n + 1) * 8), recoff_at = nrec_at + pad((size_t)n * 4);       /* SA: records per read and their scan */
-    const size_t need = recoff_at + ((size_t)n + 1) * 8;
-    if (c->paf_bytes < need) {
-        if (c->h_paf) { (void)hipHostFree(c->h_paf); c->h_paf = c->d_paf = nullptr; c->paf_bytes = 0; }
-        HIPCHK(c, hipHostMalloc((void **)&c->h_paf, need, hipHostMallocMapped));
-        void *dp = nullptr;
-        HIPCHK(c, hipHostGetDevicePointer(&dp, c->h_paf, 0));
-        c->d_paf = (uint8_t *)dp; c->paf_bytes = need;
-    }
-    uint32_t *len = (uint32_t *)(c->d_paf + len_at), *best = (uint32_t *)(c->d_paf + best_at), *n_rec = (uint32_t *)(c->d_paf + nrec_at);
-    uint64_t *off = (uint64_t *)(c->d_paf + off_at), *rec_off = (uint64_t *)(c->d_paf + recoff_at);
-    const uint8_t *arena = (const uint8_t *)c->scratch;
-    const bool sam = kind == TRUTH_SAM, bam = kind == TRUTH_BAM, depth = kind == TRUTH_DEPTH, sa = (tags & BRX_TAG_SA) != 0;
-    if (depth && ((uintptr_t)d_out & 7u)) return fail(c, BRX_E_ARG, "brx_emit_depth: the output buffer must be 8-byte aligned");
-    const uint64_t *c_off = off, *c_rec_off = rec_off;
-    const uint32_t *c_best = best;
-    auto size = [&](auto T, auto F) {
-        constexpr uint32_t TG = decltype(T)::value; constexpr bool FM = decltype(F)::value;
-        if (bam) hipLaunchKernelGGL((k_bam_size<TG, FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, max_ops, len, best, n_rec, fmt);
-        else if (sam) hipLaunchKernelGGL((k_sam_size<TG, FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len, best, n_rec, fmt);
-        else hipLaunchKernelGGL((k_paf_size<FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, fmt, len, best);
-    };
-    if (n && depth) hipLaunchKernelGGL(k_depth_size, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, len);
-    else if (n) with_tags_fmt(tags, fmt != 0, size);
-    hipLaunchKernelGGL(k_truth_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)len, off);
-    if (sa) hipLaunchKernelGGL(k_truth_scan, dim3(1), dim3(64), 0, st, n, (const uint32_t *)n_rec, rec_off);
-    { int rcw = wait_stream(c, st, depth ? "k_depth_size" : bam ? "k_bam_size" : sam ? "k_sam_size" : "k_paf_size"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    const uint64_t total = ((const uint64_t *)(c->h_paf + off_at))[n];
-    if (total > out_cap || (total && !d_out)) {
-        c->output_needed = total;
-        return fail(c, BRX_E_OUTPUT, "truth alignment buffer too small: need %llu bytes", (unsigned long long)total);
-    }
-    const uint64_t sa_recs = sa ? ((const uint64_t *)(c->h_paf + recoff_at))[n] : 0;
-    if (sa_recs * sizeof(SaRec) > c->sa_bytes) {
-        if (c->h_sa) { (void)hipHostFree(c->h_sa); c->h_sa = c->d_sa = nullptr; c->sa_bytes = 0; }
-        const size_t want = (size_t)(sa_recs + sa_recs / 4 + 1024) * sizeof(SaRec);
-        HIPCHK(c, hipHostMalloc((void **)&c->h_sa, want, hipHostMallocMapped));
-        void *dp = nullptr;
-        HIPCHK(c, hipHostGetDevicePointer(&dp, c->h_sa, 0));
-        c->d_sa = (uint8_t *)dp; c->sa_bytes = want;
-    }
-    SaRec *table = (SaRec *)c->d_sa;
-    if (n && total && sa_recs) hipLaunchKernelGGL(k_sa_fill, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, (const uint64_t *)rec_off, table);
-    const SaRec *c_table = table;
-    auto write = [&](auto T, auto F) {
-        constexpr uint32_t TG = decltype(T)::value; constexpr bool FM = decltype(F)::value;
-        if (bam) hipLaunchKernelGGL((k_bam_write<TG, FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf, max_ops,
-                                    c_off, c_best, d_out, c->paf_frags, c_rec_off, c_table, fmt);
-        else if (sam) hipLaunchKernelGGL((k_sam_write<TG, FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, c->paf_pieces, c->paf_seqbuf,
-                                         c_off, c_best, d_out, c->paf_frags, c_rec_off, c_table, fmt);
-        else hipLaunchKernelGGL((k_paf_write<FM>), dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, c->paf_seqbuf, c->paf_frags, fmt,
-                                c_off, c_best, d_out);
-    };
-    if (n && total && depth) hipLaunchKernelGGL(k_depth_write, dim3(n), dim3(64), 0, st, c->paf_dev, c->paf_rs, c->paf_segs, arena, c_off, d_out);
-    else if (n && total) with_tags_fmt(tags, fmt != 0, write);
-    if (d_read_off) HIPCHK(c, hipMemcpyAsync(d_read_off, c->h_paf + off_at, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, st));
-    { int rcw = wait_stream(c, st, depth ? "k_depth_write" : bam ? "k_bam_write" : sam ? "k_sam_write" : "k_paf_write"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    *out_bytes = (size_t)total;
-    return BRX_OK;
-}
-extern "C" int brx_emit_paf_fmt(brx_ctx *c, uint32_t fmt, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return emit_truth(c, TRUTH_PAF, fmt, 0, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
-}
-extern "C" int brx_emit_sam_fmt(brx_ctx *c, uint32_t fmt, uint32_t tags, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return emit_truth(c, TRUTH_SAM, fmt, tags, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
-}
-extern "C" int brx_emit_bam_fmt(brx_ctx *c, uint32_t fmt, uint32_t tags, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off,
-                                size_t *out_bytes, void *hip_stream) {
-    if (!c || !out_bytes) return BRX_E_ARG;
-    if (max_cigar_ops == 0) max_cigar_ops = 65535;
-    if (max_cigar_ops < 2 || max_cigar_ops > 65535) return fail(c, BRX_E_ARG, "brx_emit_bam: max_cigar_ops %u (2..65535, or 0 for 65535)", max_cigar_ops);
-    return emit_truth(c, TRUTH_BAM, fmt, tags, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
-}
-/* the functions without formats: fmt = 0 */
-extern "C" int brx_emit_paf(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return brx_emit_paf_fmt(c, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
-}
-extern "C" int brx_emit_sam_tags(brx_ctx *c, uint32_t tags, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return brx_emit_sam_fmt(c, 0, tags, d_out, out_cap, d_read_off, out_bytes, hip_stream);
-}
-extern "C" int brx_emit_sam(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return brx_emit_sam_fmt(c, 0, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
-}
-extern "C" int brx_emit_bam_tags(brx_ctx *c, uint32_t tags, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes,
-                                 void *hip_stream) {
-    return brx_emit_bam_fmt(c, 0, tags, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
-}
-extern "C" int brx_emit_bam(brx_ctx *c, uint32_t max_cigar_ops, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return brx_emit_bam_fmt(c, 0, 0, max_cigar_ops, d_out, out_cap, d_read_off, out_bytes, hip_stream);
-}
-
-/* ---- the true coverage of the reference (brx_depth.h) ---- */
-extern "C" int brx_emit_depth(brx_ctx *c, uint8_t *d_out, size_t out_cap, uint64_t *d_read_off, size_t *out_bytes, void *hip_stream) {
-    return emit_truth(c, TRUTH_DEPTH, 0, 0, 0, d_out, out_cap, d_read_off, out_bytes, hip_stream);
-}
-
-/* where brx_depth_bedgraph keeps what in its scratch, for N keys (the events and four per contig) */
-struct DpPlan { uint64_t n; uint32_t n_tiles; size_t keys_a, keys_b, gk, gd, cd, table, incl, sums, flags, bytes; };
-static DpPlan dp_plan(uint64_t n) {
-    DpPlan p; p.n = n; p.n_tiles = (uint32_t)((n + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE);
-    const uint64_t cells = 256ull * p.n_tiles, longest = std::max(n, cells);
-    size_t at = 0;
-    auto take = [&](uint64_t bytes) { const size_t here = at; at += (size_t)((bytes + 255) & ~(uint64_t)255); return here; };
-    p.keys_a = take(n * 8); p.keys_b = take(n * 8); p.gk = take(n * 8); p.gd = take(n * 4); p.cd = take(n * 4);
-    p.table = take(cells * 4); p.incl = take(cells * 8);
-    p.sums = take(((longest + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE + 1) * 8); p.flags = take(256);
-    p.bytes = at + 256;                                  /* the caller's block may begin anywhere */
-    return p;
-}
-/* one inclusive scan: out[i] = the sum of src over [0, i] */
-template <class Src> static void dp_scan(hipStream_t st, Src src, uint64_t n, uint64_t *sums, uint64_t *out) {
-    const uint32_t nt = (uint32_t)((n + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE);
-    hipLaunchKernelGGL((k_dp_reduce<Src>), dim3(nt), dim3(BRX_DP_THREADS), 0, st, src, n, sums);
-    hipLaunchKernelGGL(k_dp_scan_sums, dim3(1), dim3(BRX_DP_THREADS), 0, st, sums, nt);
-    hipLaunchKernelGGL((k_dp_apply<Src>), dim3(nt), dim3(BRX_DP_THREADS), 0, st, src, n, (const uint64_t *)sums, out);
-}
-extern "C" size_t brx_depth_bedgraph_scratch(uint64_t n_events) { return dp_plan(n_events + 4ull * BRX_DEPTH_SCRATCH_CONTIGS).bytes; }
-extern "C" int brx_depth_last(const brx_ctx *c, uint32_t *sort_passes, float ms[3]) {
-    if (!c) return BRX_E_ARG;
-    if (sort_passes) *sort_passes = c->depth_passes;
-    if (ms) memcpy(ms, c->depth_ms, sizeof(c->depth_ms));
-    return BRX_OK;
-}
-static double dp_now_ms() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e3 + t.tv_nsec * 1e-6; }
-
-extern "C" int brx_depth_bedgraph(brx_ctx *c, const uint64_t *d_events, uint64_t n_events, uint8_t *d_out, size_t out_cap, size_t *out_bytes,
-                                  void *d_scratch, size_t scratch_bytes, void *hip_stream) {
-    if (!c || !out_bytes || (n_events && !d_events) || !d_scratch) return BRX_E_ARG;
-    *out_bytes = 0;
-    if (!c->has_ref) return fail(c, BRX_E_STATE, "brx_depth_bedgraph: reference not set");
-    const brx_reference &ref = c->dev.ref;
-    if (n_events & 1u) return fail(c, BRX_E_ARG, "brx_depth_bedgraph: %llu events: every record has two", (unsigned long long)n_events);
-    if (ref.n_contigs >= (1u << 24)) return fail(c, BRX_E_ARG, "brx_depth_bedgraph: %u contigs (an event holds fewer than 2^24)", ref.n_contigs);
-    const uint64_t n = n_events + 4ull * ref.n_contigs;
-    if (n >= (1ull << 31)) return fail(c, BRX_E_ARG, "brx_depth_bedgraph: %llu events and %u contigs: fewer than 2^31 keys in one call", (unsigned long long)n_events, ref.n_contigs);
-    const DpPlan P = dp_plan(n);
-    uint8_t *base = (uint8_t *)(((uintptr_t)d_scratch + 255) & ~(uintptr_t)255);
-    if (scratch_bytes < P.bytes) {
-        c->scratch_needed = P.bytes;
-        return fail(c, BRX_E_SCRATCH, "brx_depth_bedgraph: scratch too small (%zu < %zu)", scratch_bytes, P.bytes);
-    }
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    uint64_t *keys[2] = { (uint64_t *)(base + P.keys_a), (uint64_t *)(base + P.keys_b) };
-    uint64_t *gk = (uint64_t *)(base + P.gk), *incl = (uint64_t *)(base + P.incl), *sums = (uint64_t *)(base + P.sums);
-    uint32_t *gd = (uint32_t *)(base + P.gd), *cd = (uint32_t *)(base + P.cd), *table = (uint32_t *)(base + P.table), *err = (uint32_t *)(base + P.flags);
-    const brx_contig *ct = ref.d_contigs;
-    const uint32_t nt = P.n_tiles;
-    double t0 = dp_now_ms();
-    /* the digits that can vary: the bytes of (the longest contig's length << 1 | 1) below bit 40, those of the last contig's index above */
-    uint32_t longest = 0;
-    {
-        std::vector<brx_contig> h(ref.n_contigs);
-        HIPCHK(c, hipMemcpyAsync(h.data(), ct, sizeof(brx_contig) * ref.n_contigs, hipMemcpyDeviceToHost, st));
-        { int rcw = wait_stream(c, st, "brx_depth_bedgraph (contigs)"); if (rcw) return rcw; }
-        for (const brx_contig &x : h) longest = std::max(longest, x.length);
-    }
-    uint32_t shifts[8], n_pass = 0;
-    for (uint32_t b = 0; b < 5; ++b) if (((((uint64_t)longest << 1) | 1u) >> (8 * b)) != 0) shifts[n_pass++] = 8 * b;
-    for (uint32_t b = 0; b < 3; ++b) if (((uint64_t)(ref.n_contigs - 1) >> (8 * b)) != 0) shifts[n_pass++] = 40 + 8 * b;
-    c->depth_passes = n_pass;
-    HIPCHK(c, hipMemsetAsync(err, 0, 256, st));
-    const DpSrcTable tab = { table };
-    for (uint32_t p = 0; p < n_pass; ++p) {
-        uint64_t *dst = keys[p & 1u];
-        if (p == 0) {
-            const DpKeysIn in = { d_events, n_events, ct };
-            hipLaunchKernelGGL((k_dp_hist<DpKeysIn, true>), dim3(nt), dim3(BRX_DP_THREADS), 0, st, in, n, shifts[p], nt, table, n_events, ct, ref.n_contigs, err);
-            dp_scan(st, tab, 256ull * nt, sums, incl);
-            hipLaunchKernelGGL((k_dp_scatter<DpKeysIn>), dim3(nt), dim3(BRX_DP_THREADS), 0, st, in, n, shifts[p], nt, (const uint32_t *)table, (const uint64_t *)incl, dst);
-        } else {
-            const DpKeysBuf in = { keys[(p - 1) & 1u] };
-            hipLaunchKernelGGL((k_dp_hist<DpKeysBuf, false>), dim3(nt), dim3(BRX_DP_THREADS), 0, st, in, n, shifts[p], nt, table, n_events, ct, ref.n_contigs, err);
-            dp_scan(st, tab, 256ull * nt, sums, incl);
-            hipLaunchKernelGGL((k_dp_scatter<DpKeysBuf>), dim3(nt), dim3(BRX_DP_THREADS), 0, st, in, n, shifts[p], nt, (const uint32_t *)table, (const uint64_t *)incl, dst);
-        }
-    }
-    uint64_t *sorted = keys[(n_pass - 1) & 1u], *spare = keys[n_pass & 1u];
-    uint32_t bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, err, 4, hipMemcpyDeviceToHost, st));
-    { int rcw = wait_stream(c, st, "brx_depth_bedgraph (sort)"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    if (bad) return fail(c, BRX_E_ARG, "brx_depth_bedgraph: an event names a contig outside the reference or a position beyond its contig");
-    double t1 = dp_now_ms();
-    c->depth_ms[0] = (float)(t1 - t0);
-    /* depth: from here on the keys are known to name contigs of the reference */
-    const DpSrcPack pack = { sorted, n };
-    dp_scan(st, pack, n, sums, spare);
-    hipLaunchKernelGGL(k_dp_groups, dim3((uint32_t)((n + BRX_DP_THREADS - 1) / BRX_DP_THREADS)), dim3(BRX_DP_THREADS), 0, st, (const uint64_t *)sorted, (const uint64_t *)spare, n, gk, gd, err);
-    uint64_t last = 0;
-    HIPCHK(c, hipMemcpyAsync(&last, spare + (n - 1), 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&bad, err, 4, hipMemcpyDeviceToHost, st));
-    { int rcw = wait_stream(c, st, "brx_depth_bedgraph (depth)"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    if (bad) return fail(c, BRX_E_ARG, "brx_depth_bedgraph: the events are not pairs of a start and a later end (depth below 0, or not 0 at a contig's end)");
-    const uint64_t n_groups = last >> 32;
-    const DpSrcChange change = { gk, gd, ct };
-    dp_scan(st, change, n_groups, sums, spare);
-    uint64_t *ck = sorted;                               /* the sorted keys have been read for the last time */
-    hipLaunchKernelGGL(k_dp_points, dim3((uint32_t)((n_groups + BRX_DP_THREADS - 1) / BRX_DP_THREADS)), dim3(BRX_DP_THREADS), 0, st, change, (const uint64_t *)spare, n_groups, ck, cd);
-    uint64_t n_points = 0;
-    HIPCHK(c, hipMemcpyAsync(&n_points, spare + (n_groups - 1), 8, hipMemcpyDeviceToHost, st));
-    { int rcw = wait_stream(c, st, "brx_depth_bedgraph (change points)"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    double t2 = dp_now_ms();
-    c->depth_ms[1] = (float)(t2 - t1);
-    /* text */
-    const DpSrcLine line = { ck, cd, ct };
-    dp_scan(st, line, n_points, sums, spare);
-    uint64_t total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, spare + (n_points - 1), 8, hipMemcpyDeviceToHost, st));
-    { int rcw = wait_stream(c, st, "brx_depth_bedgraph (line sizes)"); if (rcw) return rcw; }
-    if (total > out_cap || (total && !d_out)) {
-        c->output_needed = (size_t)total;
-        return fail(c, BRX_E_OUTPUT, "brx_depth_bedgraph: output buffer too small: need %llu bytes", (unsigned long long)total);
-    }
-    hipLaunchKernelGGL(k_dp_lines, dim3((uint32_t)((n_points + BRX_DP_THREADS - 1) / BRX_DP_THREADS)), dim3(BRX_DP_THREADS), 0, st, line, (const uint64_t *)spare, n_points, ref.d_names, d_out);
-    { int rcw = wait_stream(c, st, "brx_depth_bedgraph (text)"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    c->depth_ms[2] = (float)(dp_now_ms() - t2);
-    *out_bytes = (size_t)total;
-    return BRX_OK;
-}
-
-/* ---- window identities (brx_window.h) ---- */
-struct PwPlan { uint32_t n_tiles; size_t err, pe, pq, sums, bytes; };
-static PwPlan pw_plan(uint64_t n_bases, int want_qual) {
-    PwPlan p; p.n_tiles = (uint32_t)((n_bases + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE);
-    size_t at = 0;
-    auto take = [&](uint64_t bytes) { const size_t here = at; at += (size_t)((bytes + 255) & ~(uint64_t)255); return here; };
-    p.err = take(n_bases * 4); p.pe = take((n_bases + 1) * 8); p.pq = take(want_qual ? (n_bases + 1) * 8 : 0);
-    p.sums = take(((uint64_t)p.n_tiles + 1) * 8);
-    p.bytes = at + 256;                                  /* the caller's block may begin anywhere */
-    return p;
-}
-extern "C" size_t brx_window_scratch(uint64_t n_bases, int want_qual) { return pw_plan(n_bases, want_qual).bytes; }
-extern "C" int brx_window_last(const brx_ctx *c, float ms[4]) {
-    if (!c || !ms) return BRX_E_ARG;
-    memcpy(ms, c->window_ms, sizeof(c->window_ms));
-    return BRX_OK;
-}
-extern "C" int brx_window_means(brx_ctx *c, const brx_window_job *job, void *hip_stream) {
-    if (!c || !job) return BRX_E_ARG;
-    const brx_window_job j = *job;
-    if (j.window == 0) return fail(c, BRX_E_ARG, "brx_window_means: window 0");
-    if (j.n_align == 0) return BRX_OK;
-    if (!j.d_align_read_off || !j.d_align_part_off || !j.d_align_win_off || !j.d_stat) return fail(c, BRX_E_ARG, "brx_window_means: an offset array or d_stat is NULL");
-    if (j.n_bases && (!j.d_seq || !j.d_ref || !j.d_part_type || !j.d_part_len || !j.d_part_read || !j.d_part_ref || (j.want_qual && !j.d_qual)))
-        return fail(c, BRX_E_ARG, "brx_window_means: a slice or part array is NULL");
-    if (j.n_bases >= (1ull << 39)) return fail(c, BRX_E_ARG, "brx_window_means: %llu read bases: fewer than 2^39 in one call", (unsigned long long)j.n_bases);
-    if (j.n_windows > j.n_bases) return fail(c, BRX_E_ARG, "brx_window_means: more windows than read bases");
-    const PwPlan P = pw_plan(j.n_bases, (int)j.want_qual);
-    if (!j.d_scratch || j.scratch_bytes < P.bytes) {
-        c->scratch_needed = P.bytes;
-        return fail(c, BRX_E_SCRATCH, "brx_window_means: scratch too small (%zu < %zu)", j.scratch_bytes, P.bytes);
-    }
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    uint8_t *base = (uint8_t *)(((uintptr_t)j.d_scratch + 255) & ~(uintptr_t)255);
-    uint32_t *err = (uint32_t *)(base + P.err);
-    uint64_t *pe = (uint64_t *)(base + P.pe), *pq = j.want_qual ? (uint64_t *)(base + P.pq) : nullptr, *sums = (uint64_t *)(base + P.sums);
-    const bool timed = c->ktiming && c->kev_b[0];            /* the event pool of brx_set_kernel_timing: five marks */
-    auto mark = [&](int i) { if (timed) (void)hipEventRecord(c->kev_b[i], st); };
-    mark(0);
-    if (j.n_bases) {
-        hipLaunchKernelGGL(k_pw_errors, dim3((uint32_t)((j.n_bases + BRX_PW_THREADS - 1) / BRX_PW_THREADS)), dim3(BRX_PW_THREADS), 0, st, j, err, pe, pq);
-        mark(1);
-        const DpSrcTable e = { err };
-        dp_scan(st, e, j.n_bases, sums, pe + 1);
-        if (pq) { const PwSrcQual q = { j.d_qual }; dp_scan(st, q, j.n_bases, sums, pq + 1); }
-    } else mark(1);
-    mark(2);
-    hipLaunchKernelGGL(k_pw_stats, dim3(j.n_align), dim3(BRX_PW_THREADS), 0, st, j, (const uint64_t *)pe, (const uint64_t *)pq);
-    mark(3);
-    if (j.n_windows && (j.d_err_sum || j.d_qual_sum))
-        hipLaunchKernelGGL(k_pw_values, dim3((uint32_t)((j.n_windows + BRX_PW_THREADS - 1) / BRX_PW_THREADS)), dim3(BRX_PW_THREADS), 0, st, j, (const uint64_t *)pe, (const uint64_t *)pq);
-    mark(4);
-    { int rcw = wait_stream(c, st, "brx_window_means"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    if (timed) for (int i = 0; i < 4; ++i) HIPCHK(c, hipEventElapsedTime(&c->window_ms[i], c->kev_b[i], c->kev_b[i + 1]));
-    return BRX_OK;
-}
-
-/* ---- the device loader (brx_pafin.h) ---- */
-struct PiPlan { uint32_t n_tiles; size_t incl, sums, flags, bytes; };
-static PiPlan pi_plan(uint64_t n_bytes) {
-    PiPlan p; p.n_tiles = (uint32_t)((n_bytes + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE);
-    size_t at = 0;
-    auto take = [&](uint64_t bytes) { const size_t here = at; at += (size_t)((bytes + 255) & ~(uint64_t)255); return here; };
-    p.incl = take(n_bytes * 8); p.sums = take(((uint64_t)p.n_tiles + 1) * 8); p.flags = take(256);
-    p.bytes = at + 256;                                  /* the caller's block may begin anywhere */
-    return p;
-}
-extern "C" size_t brx_paf_scan_scratch(uint64_t n_bytes) { return pi_plan(n_bytes).bytes; }
-extern "C" int brx_loader_last(const brx_ctx *c, float ms[2]) {
-    if (!c || !ms) return BRX_E_ARG;
-    memcpy(ms, c->loader_ms, sizeof(c->loader_ms));
-    return BRX_OK;
-}
-extern "C" int brx_paf_scan(brx_ctx *c, const uint8_t *d_text, uint64_t n_bytes, uint64_t max_lines, brx_paf_line *d_lines, uint64_t line_cap,
-                            uint64_t *n_lines, void *d_scratch, size_t scratch_bytes, void *hip_stream) {
-    if (!c) return BRX_E_ARG;
-    if (!n_lines) return fail(c, BRX_E_ARG, "brx_paf_scan: n_lines is NULL");
-    *n_lines = 0;
-    if (n_bytes == 0) return BRX_OK;
-    if (!d_text) return fail(c, BRX_E_ARG, "brx_paf_scan: d_text is NULL");
-    if (n_bytes >= (1ull << 42)) return fail(c, BRX_E_ARG, "brx_paf_scan: %llu bytes: fewer than 2^42 in one call", (unsigned long long)n_bytes);
-    const PiPlan P = pi_plan(n_bytes);
-    if (!d_scratch || scratch_bytes < P.bytes) {
-        c->scratch_needed = P.bytes;
-        return fail(c, BRX_E_SCRATCH, "brx_paf_scan: scratch too small (%zu < %zu)", d_scratch ? scratch_bytes : (size_t)0, P.bytes);
-    }
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    uint8_t *base = (uint8_t *)(((uintptr_t)d_scratch + 255) & ~(uintptr_t)255);
-    uint64_t *incl = (uint64_t *)(base + P.incl), *sums = (uint64_t *)(base + P.sums);
-    uint32_t *err = (uint32_t *)(base + P.flags);
-    const bool timed = c->ktiming && c->kev_b[0];
-    if (timed) (void)hipEventRecord(c->kev_b[0], st);
-    HIPCHK(c, hipMemsetAsync(err, 0, 256, st));
-    const PiSrcStart start = { d_text };
-    dp_scan(st, start, n_bytes, sums, incl);
-    uint64_t total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, incl + (n_bytes - 1), 8, hipMemcpyDeviceToHost, st));
-    { int rcw = wait_stream(c, st, "brx_paf_scan (line starts)"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    const uint64_t n = max_lines && max_lines < total ? max_lines : total;
-    if (n >= (1ull << 31)) return fail(c, BRX_E_ARG, "brx_paf_scan: %llu lines: fewer than 2^31 in one call", (unsigned long long)n);
-    if (n > line_cap || !d_lines) {
-        c->output_needed = (size_t)n;
-        return fail(c, BRX_E_OUTPUT, "brx_paf_scan: room for %llu records, %llu lines", (unsigned long long)(d_lines ? line_cap : 0), (unsigned long long)n);
-    }
-    hipLaunchKernelGGL(k_pi_starts, dim3((uint32_t)((n_bytes + BRX_PI_THREADS - 1) / BRX_PI_THREADS)), dim3(BRX_PI_THREADS), 0, st, start, n_bytes, (const uint64_t *)incl, n, d_lines);
-    hipLaunchKernelGGL(k_pi_lines, dim3((uint32_t)n), dim3(64), 0, st, d_text, n_bytes, d_lines, err);
-    uint32_t bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, err, 4, hipMemcpyDeviceToHost, st));
-    if (timed) (void)hipEventRecord(c->kev_b[1], st);
-    { int rcw = wait_stream(c, st, "brx_paf_scan"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    if (timed) HIPCHK(c, hipEventElapsedTime(&c->loader_ms[0], c->kev_b[0], c->kev_b[1]));
-    if (bad) return fail(c, BRX_E_ARG, "brx_paf_scan: a line of 2^32 bytes or more");
-    *n_lines = n;
-    return BRX_OK;
-}
-
-extern "C" int brx_align_pack(brx_ctx *c, const brx_pack_job *job, void *hip_stream) {
-    if (!c || !job) return BRX_E_ARG;
-    const brx_pack_job j = *job;
-    if (j.n_align == 0) return BRX_OK;
-    if (!j.d_align || !j.d_align_part_off || !j.d_align_col_off || !j.d_align_read_off || !j.d_align_ref_off)
-        return fail(c, BRX_E_ARG, "brx_align_pack: d_align or an offset array is NULL");
-    if (!j.d_text || !j.d_reftext || !j.d_complement || !j.d_part_type || !j.d_part_len || !j.d_part_col || !j.d_part_read || !j.d_part_ref || !j.d_ref || !j.d_flags)
-        return fail(c, BRX_E_ARG, "brx_align_pack: a text, the complement table, an output array or d_flags is NULL");
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    const bool timed = c->ktiming && c->kev_b[0];
-    if (timed) (void)hipEventRecord(c->kev_b[0], st);
-    hipLaunchKernelGGL(k_pi_pack, dim3(j.n_align), dim3(64), 0, st, j, j.d_flags);
-    if (timed) (void)hipEventRecord(c->kev_b[1], st);
-    uint32_t bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, j.d_flags, 4, hipMemcpyDeviceToHost, st));
-    { int rcw = wait_stream(c, st, "brx_align_pack"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    if (timed) HIPCHK(c, hipEventElapsedTime(&c->loader_ms[1], c->kev_b[0], c->kev_b[1]));
-    if (bad) return fail(c, BRX_E_ARG, "brx_align_pack: an alignment's descriptor does not fit its CIGAR, the texts or the offset arrays");
-    return BRX_OK;
-}
-
-/* ---- the device read loader (brx_fastqin.h) ---- */
-/* where brx_fastq_scan keeps what in its scratch: the scan's prefix per group of 16 bytes, the tile sums, the flags, the line starts */
-struct FqPlan { uint64_t n_groups; uint32_t n_tiles; size_t incl, sums, flags, lines, bytes; };
-static FqPlan fq_plan(uint64_t n_bytes, uint64_t n_lines) {
-    FqPlan p; p.n_groups = (n_bytes + 15) / 16; p.n_tiles = (uint32_t)((p.n_groups + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE);
-    size_t at = 0;
-    auto take = [&](uint64_t bytes) { const size_t here = at; at += (size_t)((bytes + 255) & ~(uint64_t)255); return here; };
-    p.incl = take(p.n_groups * 8); p.sums = take(((uint64_t)p.n_tiles + 1) * 8); p.flags = take(256); p.lines = take((n_lines + 1) * 8);
-    p.bytes = at + 256;                                  /* the caller's block may begin anywhere */
-    return p;
-}
-extern "C" size_t brx_fastq_scan_scratch(uint64_t n_bytes) { return fq_plan(n_bytes, n_bytes / 64 + 64).bytes; }
-extern "C" int brx_reads_last(const brx_ctx *c, float ms[2]) {
-    if (!c || !ms) return BRX_E_ARG;
-    memcpy(ms, c->reads_ms, sizeof(c->reads_ms));
-    return BRX_OK;
-}
-extern "C" int brx_fastq_scan(brx_ctx *c, const uint8_t *d_text, uint64_t n_bytes, brx_fastq_rec *d_recs, uint64_t rec_cap, uint64_t *n_recs,
-                              uint32_t *layout, void *d_scratch, size_t scratch_bytes, void *hip_stream) {
-    if (!c) return BRX_E_ARG;
-    if (!n_recs || !layout) return fail(c, BRX_E_ARG, "brx_fastq_scan: n_recs or layout is NULL");
-    *n_recs = 0; *layout = 0;
-    if (n_bytes == 0) return BRX_OK;
-    if (!d_text) return fail(c, BRX_E_ARG, "brx_fastq_scan: d_text is NULL");
-    if (n_bytes >= (1ull << 42)) return fail(c, BRX_E_ARG, "brx_fastq_scan: %llu bytes: fewer than 2^42 in one call", (unsigned long long)n_bytes);
-    const size_t least = brx_fastq_scan_scratch(n_bytes);
-    if (!d_scratch || scratch_bytes < least) {
-        c->scratch_needed = least;
-        return fail(c, BRX_E_SCRATCH, "brx_fastq_scan: scratch too small (%zu < %zu)", d_scratch ? scratch_bytes : (size_t)0, least);
-    }
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    uint8_t *base = (uint8_t *)(((uintptr_t)d_scratch + 255) & ~(uintptr_t)255);
-    FqPlan P = fq_plan(n_bytes, 0);
-    uint64_t *incl = (uint64_t *)(base + P.incl), *sums = (uint64_t *)(base + P.sums);
-    uint32_t *flags = (uint32_t *)(base + P.flags);
-    const bool timed = c->ktiming && c->kev_b[0];
-    if (timed) (void)hipEventRecord(c->kev_b[0], st);
-    HIPCHK(c, hipMemsetAsync(flags, 0, 256, st));
-    const FqSrcStarts16 src = { d_text, n_bytes };
-    dp_scan(st, src, P.n_groups, sums, incl);
-    uint64_t n_lines = 0;
-    HIPCHK(c, hipMemcpyAsync(&n_lines, incl + (P.n_groups - 1), 8, hipMemcpyDeviceToHost, st));
-    { int rcw = wait_stream(c, st, "brx_fastq_scan (line starts)"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    if (n_lines & 3u) { *layout = BRX_FQ_LINES; return BRX_OK; }
-    const uint64_t n = n_lines / 4;
-    if (n >= (1ull << 31)) return fail(c, BRX_E_ARG, "brx_fastq_scan: %llu records: fewer than 2^31 in one call", (unsigned long long)n);
-    if (n > rec_cap || !d_recs) {
-        c->output_needed = (size_t)n;
-        return fail(c, BRX_E_OUTPUT, "brx_fastq_scan: room for %llu records, %llu in the file", (unsigned long long)(d_recs ? rec_cap : 0), (unsigned long long)n);
-    }
-    P = fq_plan(n_bytes, n_lines);
-    if (scratch_bytes < P.bytes) {
-        c->scratch_needed = P.bytes;
-        return fail(c, BRX_E_SCRATCH, "brx_fastq_scan: scratch too small for %llu lines (%zu < %zu)", (unsigned long long)n_lines, scratch_bytes, P.bytes);
-    }
-    uint64_t *line_start = (uint64_t *)(base + P.lines);
-    hipLaunchKernelGGL(k_fq_starts, dim3((uint32_t)((P.n_groups + BRX_FQ_THREADS - 1) / BRX_FQ_THREADS)), dim3(BRX_FQ_THREADS), 0, st, src, P.n_groups, (const uint64_t *)incl, line_start, flags);
-    hipLaunchKernelGGL(k_fq_records, dim3((uint32_t)((n + BRX_FQ_THREADS - 1) / BRX_FQ_THREADS)), dim3(BRX_FQ_THREADS), 0, st, d_text, (const uint64_t *)line_start, n, d_recs, flags);
-    uint32_t got[3] = { 0, 0, 0 };
-    HIPCHK(c, hipMemcpyAsync(got, flags, sizeof(got), hipMemcpyDeviceToHost, st));
-    if (timed) (void)hipEventRecord(c->kev_b[1], st);
-    { int rcw = wait_stream(c, st, "brx_fastq_scan"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    if (timed) HIPCHK(c, hipEventElapsedTime(&c->reads_ms[0], c->kev_b[0], c->kev_b[1]));
-    if (got[2]) return fail(c, BRX_E_ARG, "brx_fastq_scan: a line of 2^32 bytes or more");
-    *layout = (got[0] ? BRX_FQ_HIGH : 0u) | (got[1] ? BRX_FQ_HEADER : 0u);
-    if (*layout == 0) *n_recs = n;
-    return BRX_OK;
-}
-
-extern "C" int brx_reads_pack(brx_ctx *c, const brx_reads_job *job, void *hip_stream) {
-    if (!c || !job) return BRX_E_ARG;
-    const brx_reads_job j = *job;
-    if (j.n_align == 0) return BRX_OK;
-    if (!j.d_seq_src || !j.d_qual_src || !j.d_align_read_off) return fail(c, BRX_E_ARG, "brx_reads_pack: a source or offset array is NULL");
-    if (!j.d_text || !j.d_seq || !j.d_qual || !j.d_flags) return fail(c, BRX_E_ARG, "brx_reads_pack: the text, an output array or d_flags is NULL");
-    hipStream_t st = (hipStream_t)hip_stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    const bool timed = c->ktiming && c->kev_b[0];
-    if (timed) (void)hipEventRecord(c->kev_b[0], st);
-    hipLaunchKernelGGL(k_fq_check, dim3((j.n_align + BRX_FQ_THREADS - 1) / BRX_FQ_THREADS), dim3(BRX_FQ_THREADS), 0, st, j, j.d_flags);
-    uint32_t bad = 0;
-    uint64_t total = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, j.d_flags, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&total, j.d_align_read_off + j.n_align, 8, hipMemcpyDeviceToHost, st));
-    { int rcw = wait_stream(c, st, "brx_reads_pack (check)"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    if (bad) return fail(c, BRX_E_ARG, "brx_reads_pack: the offsets do not ascend from 0, or a source range leaves the text");
-    const uint64_t n_tiles = (total + BRX_FQ_TILE - 1) / BRX_FQ_TILE;
-    if (n_tiles >= (1ull << 31)) return fail(c, BRX_E_ARG, "brx_reads_pack: %llu read bases: fewer than 2^43 in one call", (unsigned long long)total);
-    if (n_tiles) hipLaunchKernelGGL(k_fq_pack, dim3((uint32_t)n_tiles), dim3(BRX_FQ_THREADS), 0, st, j, total, ((uintptr_t)j.d_text & 3u) == 0);
-    if (timed) (void)hipEventRecord(c->kev_b[1], st);
-    { int rcw = wait_stream(c, st, "brx_reads_pack"); if (rcw) return rcw; }
-    HIPCHK(c, hipGetLastError());
-    if (timed) HIPCHK(c, hipEventElapsedTime(&c->reads_ms[1], c->kev_b[0], c->kev_b[1]));
-    return BRX_OK;
-}
+/* the tool calls: model builders, gzip members, truth output, depth, window identities, the device loaders */
+#include "brx_tools.h"

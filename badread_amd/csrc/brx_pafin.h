@@ -1,10 +1,10 @@
 /*
  * brx_pafin.h -- the PAF that `error_model`, `qscore_model` and `plot` read, parsed and packed on the device (--gpu-loader; README: The
- * device loader).  Included once by brx_hip.hip after brx_window.h; the scan is that of brx_depth.h.
+ * device loader).  The scan is that of brx_scan.h.
  *   Alignment.__init__   /root/reference/badread/alignment.py:24-64   (the fields, cg:Z:, AS:i:, the CIGAR's parts)
  *   Job.__init__         badread_amd/model_builder.py                 (the part arrays and the reference slices)
  * brx_paf_scan: text -> one brx_paf_line per line.
- *   1. the scan of brx_depth.h over PiSrcStart (1 for byte 0 and for every byte behind a '\n'); k_pi_starts leaves every line's first byte
+ *   1. the scan of brx_scan.h over PiSrcStart (1 for byte 0 and for every byte behind a '\n'); k_pi_starts leaves every line's first byte
  *      in its record.  Nothing is written for the lines beyond max_lines.
  *   2. k_pi_lines, a wave per line.  First the fields, 64 bytes per step: the tabs and the line's end come from ballots, and the lane that
  *      holds the delimiter BEHIND a field owns the field -- it knows where the field began (the delimiter before it, in this step or carried)
@@ -18,6 +18,8 @@
  */
 #ifndef BRX_PAFIN_H
 #define BRX_PAFIN_H
+
+#include "brx_scan.h"
 
 #define BRX_PI_THREADS 256u
 

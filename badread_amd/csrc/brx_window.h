@@ -1,7 +1,7 @@
 /*
  * brx_window.h -- the `plot` command's numbers (README: Window identities): the errors of every read base of a set of read-to-reference
- * alignments and, of every alignment, the sums of its windows of W read bases.  Included once by brx_hip.hip after brx_depth.h, whose
- * scan it uses.
+ * alignments and, of every alignment, the sums of its windows of W read bases.  The prefix sums are the tile
+ * scan of brx_scan.h.
  *   align_sequences    /root/reference/badread/alignment.py:103-132       (errors_per_read_pos)
  *   get_window_means   /root/reference/badread/plot_window_identity.py:54-70
  * The reference walks every alignment in Python, one base and then one window at a time.  Here the host ships what brx_model_count
@@ -11,7 +11,7 @@
  *      part_read, the last part that begins at or before p.  A D part takes no read base, so it shares its offset with the part behind
  *      it and the search passes over it; the thread of the FIRST base of a part walks back over the D parts in front of it and adds
  *      their lengths.  A base behind the CIGAR's last read base gets 0, or a trailing deletion's length if it is the first such base.
- *   2. the scan of brx_depth.h (k_dp_reduce, k_dp_scan_sums, k_dp_apply) over E, and over q = quality byte - 33 when asked, written
+ *   2. the scan of brx_scan.h (k_dp_reduce, k_dp_scan_sums, k_dp_apply) over E, and over q = quality byte - 33 when asked, written
  *      behind a leading 0: P[p + 1] = E[0] + .. + E[p].  No segments: a window sum is P[g + i + W] - P[g + i] inside one alignment
  *      (g: its first base), and 32 bits of it are exact as no alignment has 2^31 columns (negative q: two's complement, as exact).
  *   3. k_pw_stats: a workgroup per alignment strides over its n = max(L - W, 0) windows: min, max, the first window of the max and
@@ -23,6 +23,8 @@
  */
 #ifndef BRX_WINDOW_H
 #define BRX_WINDOW_H
+
+#include "brx_scan.h"
 
 #define BRX_PW_THREADS 256u
 

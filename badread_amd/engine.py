@@ -538,6 +538,46 @@ class HipEngine(EngineBase):
         torch.cuda.current_stream(self.device).synchronize()
         return t.data_ptr(), t
 
+    def _uploader(self):
+        """up(arr) -> the device pointer of arr's copy (of arr itself, if it is a tensor there); the copies live as long as `up` does."""
+        keep = []
+
+        def up(arr):
+            ptr, t = self._upload(arr)
+            keep.append(t)
+            return ptr
+        return up
+
+    def _sized_call(self, call, attempts, out, scratch=None):
+        """One of the library's sized calls: rc = call(out_tensor, out_capacity, scratch_tensor), at most `attempts` times, for as long as
+        rc is E_OUTPUT or E_SCRATCH and that buffer grows.  out / scratch: (first capacity, make(capacity) -> tensor, grow(needed,
+        capacity) -> the next capacity, or None: stop); scratch None: the caller's own, E_SCRATCH is final.  A buffer is made again only
+        when its capacity has changed (the library writes nothing into either before it answers with one of the two).  Raises on the
+        last rc if it is an error; returns the output tensor."""
+        specs = {E_OUTPUT: out, E_SCRATCH: scratch}
+        needed = {E_OUTPUT: self.lib.brx_output_needed, E_SCRATCH: self.lib.brx_scratch_needed}
+        size = {k: spec[0] for k, spec in specs.items() if spec}
+        made, bufs = {}, {E_OUTPUT: None, E_SCRATCH: None}
+        for _ in range(attempts):
+            for k in size:
+                if made.get(k) != size[k]:
+                    bufs[k] = None                           # the old block goes before the new one comes
+                    bufs[k], made[k] = specs[k][1](size[k]), size[k]
+            rc = call(bufs[E_OUTPUT], size[E_OUTPUT], bufs[E_SCRATCH])
+            grow = specs[rc][2] if specs.get(rc) else None
+            nxt = grow(int(needed[rc](self.ctx)), size[rc]) if grow else None
+            if nxt is None:
+                break
+            size[rc] = nxt
+        self._check(rc)
+        return bufs[E_OUTPUT]
+
+    def _last_ms(self, fn, names):
+        """{name: ms} of one of the library's *_last getters, which fill one float per name."""
+        ms = (ctypes.c_float * len(names))()
+        self._check(fn(self.ctx, ctypes.byref(ms)))
+        return dict(zip(names, [float(x) for x in ms]))
+
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -702,14 +742,10 @@ class HipEngine(EngineBase):
         scratch = torch.empty(step(int(self.lib.brx_bgzf_device_scratch(n)) + 8), dtype=torch.uint8, device=self.device)
         cap = min(int(0.7 * n) + 200 * -(-n // 32768) + 4096, int(self.lib.brx_bgzf_device_bound(n)) + 8)
         got = ctypes.c_size_t(0)
-        for _ in range(2):
-            out = torch.empty(step(cap), dtype=torch.uint8, device=self.device)
-            rc = self.lib.brx_bgzf_device(self.ctx, ctypes.c_void_p(data.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), out.numel(),
-                                          ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), ctypes.byref(got), self._stream())
-            if rc != E_OUTPUT:
-                break
-            cap = int(self.lib.brx_output_needed(self.ctx)) + 8
-        self._check(rc)
+        out = self._sized_call(lambda out, _, scr: self.lib.brx_bgzf_device(
+            self.ctx, ctypes.c_void_p(data.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), out.numel(),
+            ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), ctypes.byref(got), self._stream()), 2,
+            (cap, lambda c: torch.empty(step(c), dtype=torch.uint8, device=self.device), lambda need, c: need + 8))
         return out[:got.value]
 
     def depth_bedgraph(self, events, cap=None):
@@ -720,21 +756,13 @@ class HipEngine(EngineBase):
         torch = self.torch
         events = events.contiguous().view(torch.int64)
         n = int(events.numel())
-        scratch_bytes = int(self.lib.brx_depth_bedgraph_scratch(n))
         cap = int(cap) if cap is not None else 28 * n + (1 << 16)
         got = ctypes.c_size_t(0)
-        for _ in range(3):
-            scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=self.device)
-            out = torch.zeros(max(cap, 8), dtype=torch.uint8, device=self.device)
-            rc = self.lib.brx_depth_bedgraph(self.ctx, ctypes.c_void_p(events.data_ptr()) if n else None, n, ctypes.c_void_p(out.data_ptr()), cap,
-                                             ctypes.byref(got), ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), self._stream())
-            if rc == E_OUTPUT:
-                cap = int(self.lib.brx_output_needed(self.ctx))
-            elif rc == E_SCRATCH:
-                scratch_bytes = int(self.lib.brx_scratch_needed(self.ctx))
-            else:
-                break
-        self._check(rc)
+        out = self._sized_call(lambda out, cap, scr: self.lib.brx_depth_bedgraph(
+            self.ctx, ctypes.c_void_p(events.data_ptr()) if n else None, n, ctypes.c_void_p(out.data_ptr()), cap,
+            ctypes.byref(got), ctypes.c_void_p(scr.data_ptr()), scr.numel(), self._stream()), 3,
+            (cap, lambda c: torch.zeros(max(c, 8), dtype=torch.uint8, device=self.device), lambda need, c: need),
+            (int(self.lib.brx_depth_bedgraph_scratch(n)), lambda b: torch.empty(b, dtype=torch.uint8, device=self.device), lambda need, b: need))
         return out[:got.value]
 
     def depth_last(self):
@@ -748,14 +776,10 @@ class HipEngine(EngineBase):
         torch = self.torch
         off = torch.zeros(n_reads + 1, dtype=torch.int64, device=self.device)
         cap = int(n_reads * share * self.expected_record_bytes()) + (1 << 16)
-        for _ in range(2):
-            out = torch.empty(cap, dtype=torch.uint8, device=self.device)
-            got = ctypes.c_size_t(0)
-            rc = emit(self.ctx, ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(off.data_ptr()), ctypes.byref(got), self._stream())
-            if rc != E_OUTPUT:
-                break
-            cap = int(self.lib.brx_output_needed(self.ctx)) + 64
-        self._check(rc)
+        got = ctypes.c_size_t(0)
+        out = self._sized_call(lambda out, _, scr: emit(
+            self.ctx, ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(off.data_ptr()), ctypes.byref(got), self._stream()), 2,
+            (cap, lambda c: torch.empty(c, dtype=torch.uint8, device=self.device), lambda need, c: need + 64))
         return out[:got.value], off.cpu().numpy().view(np.uint64)
 
     def simulate_batch(self, seed, first_read, n_reads, allow_nofrag=False):
@@ -831,12 +855,7 @@ class HipEngine(EngineBase):
         """brx_model_count over a model_builder.Job: (keys, counts, earliest ranks) of the occupied table slots and the
         spilled windows, or None when a table of 2^table_bits slots was too small."""
         torch = self.torch
-        keep = []
-
-        def up(arr):
-            ptr, t = self._upload(arr)
-            keep.append(t)
-            return ptr
+        up = self._uploader()
         size = 1 << table_bits
         dev = self.device
         keys = torch.full((size,), -1, dtype=torch.int64, device=dev)
@@ -873,12 +892,7 @@ class HipEngine(EngineBase):
         of stats['n']), None unless `values`, qual_sum None without `qual`.  The doubles of the reference are made from these
         integers by the caller (plot_window_identity.py)."""
         torch = self.torch
-        keep = []
-
-        def up(arr):
-            ptr, t = self._upload(arr)
-            keep.append(t)
-            return ptr
+        up = self._uploader()
         dev = self.device
         lengths = np.diff(job.align_read_off.astype(np.int64))
         n_win = np.maximum(lengths - int(window), 0)
@@ -917,14 +931,10 @@ class HipEngine(EngineBase):
             cap = min(cap, max_lines)
         scratch = torch.empty(int(self.lib.brx_paf_scan_scratch(n)), dtype=torch.uint8, device=self.device)
         got = ctypes.c_uint64(0)
-        for _ in range(2):
-            lines = torch.zeros(max(cap, 1) * PAF_LINE_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-            rc = self.lib.brx_paf_scan(self.ctx, ctypes.c_void_p(text.data_ptr()), n, max_lines, ctypes.c_void_p(lines.data_ptr()), cap,
-                                       ctypes.byref(got), ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), self._stream())
-            if rc != E_OUTPUT:
-                break
-            cap = int(self.lib.brx_output_needed(self.ctx))
-        self._check(rc)
+        lines = self._sized_call(lambda lines, cap, scr: self.lib.brx_paf_scan(
+            self.ctx, ctypes.c_void_p(text.data_ptr()), n, max_lines, ctypes.c_void_p(lines.data_ptr()), cap,
+            ctypes.byref(got), ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), self._stream()), 2,
+            (cap, lambda c: torch.zeros(max(c, 1) * PAF_LINE_DTYPE.itemsize, dtype=torch.uint8, device=self.device), lambda need, c: need))
         return np.frombuffer(lines[:got.value * PAF_LINE_DTYPE.itemsize].cpu().numpy().tobytes(), dtype=PAF_LINE_DTYPE)
 
     def align_pack(self, text, reftext, complement, aligns, part_off, col_off, read_off, ref_off):
@@ -944,12 +954,7 @@ class HipEngine(EngineBase):
                    ref=torch.zeros(max(n_ref, 1), dtype=torch.uint8, device=dev))
         if n_align == 0:
             return out
-        keep = []
-
-        def up(arr):
-            ptr, t = self._upload(arr)
-            keep.append(t)
-            return ptr
+        up = self._uploader()
         flags = torch.zeros(4, dtype=torch.int32, device=dev)
         s = BrxPackJob()
         s.n_align = n_align
@@ -965,9 +970,7 @@ class HipEngine(EngineBase):
 
     def loader_last(self):
         """ms of the last paf_scan and the last align_pack under set_kernel_timing."""
-        ms = (ctypes.c_float * 2)()
-        self._check(self.lib.brx_loader_last(self.ctx, ctypes.byref(ms)))
-        return dict(zip(('scan', 'pack'), [float(x) for x in ms]))
+        return self._last_ms(self.lib.brx_loader_last, ('scan', 'pack'))
 
     def fastq_scan(self, text, cap=None):
         """brx_fastq_scan: FASTQ text as a uint8 tensor on this engine's device -> (a numpy array of FASTQ_REC_DTYPE, one record per four
@@ -979,26 +982,13 @@ class HipEngine(EngineBase):
         if n == 0:
             return np.zeros(0, dtype=FASTQ_REC_DTYPE), 0
         cap = int(cap) if cap is not None else n // 1024 + 64
-        room = int(self.lib.brx_fastq_scan_scratch(n))
         got, layout = ctypes.c_uint64(0), ctypes.c_uint32(0)
-        recs = scratch = None
-        for _ in range(3):
-            if scratch is None or scratch.numel() < room:
-                scratch = None
-                scratch = torch.empty(room, dtype=torch.uint8, device=self.device)
-            if recs is None or recs.numel() < cap * FASTQ_REC_DTYPE.itemsize:
-                recs = None
-                recs = torch.zeros(max(cap, 1) * FASTQ_REC_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
-            rc = self.lib.brx_fastq_scan(self.ctx, ctypes.c_void_p(text.data_ptr()), n, ctypes.c_void_p(recs.data_ptr()), cap,
-                                         ctypes.byref(got), ctypes.byref(layout), ctypes.c_void_p(scratch.data_ptr()), scratch.numel(),
-                                         self._stream())
-            if rc == E_OUTPUT and cap < int(self.lib.brx_output_needed(self.ctx)):
-                cap = int(self.lib.brx_output_needed(self.ctx))
-            elif rc == E_SCRATCH and room < int(self.lib.brx_scratch_needed(self.ctx)):
-                room = int(self.lib.brx_scratch_needed(self.ctx))
-            else:
-                break
-        self._check(rc)
+        larger = lambda need, have: need if need > have else None
+        recs = self._sized_call(lambda recs, cap, scr: self.lib.brx_fastq_scan(
+            self.ctx, ctypes.c_void_p(text.data_ptr()), n, ctypes.c_void_p(recs.data_ptr()), cap,
+            ctypes.byref(got), ctypes.byref(layout), ctypes.c_void_p(scr.data_ptr()), scr.numel(), self._stream()), 3,
+            (cap, lambda c: torch.zeros(max(c, 1) * FASTQ_REC_DTYPE.itemsize, dtype=torch.uint8, device=self.device), larger),
+            (int(self.lib.brx_fastq_scan_scratch(n)), lambda b: torch.empty(b, dtype=torch.uint8, device=self.device), larger))
         return np.frombuffer(recs[:got.value * FASTQ_REC_DTYPE.itemsize].cpu().numpy().tobytes(), dtype=FASTQ_REC_DTYPE), int(layout.value)
 
     def reads_pack(self, text, seq_src, qual_src, read_off):
@@ -1010,12 +1000,7 @@ class HipEngine(EngineBase):
         if n_align == 0 or n_bases == 0:
             return tuple(torch.zeros(1, dtype=torch.uint8, device=self.device) for _ in range(2))
         seq, qual = (torch.empty(n_bases, dtype=torch.uint8, device=self.device) for _ in range(2))
-        keep = []
-
-        def up(arr):
-            ptr, t = self._upload(arr)
-            keep.append(t)
-            return ptr
+        up = self._uploader()
         flags = torch.zeros(4, dtype=torch.int32, device=self.device)
         s = BrxReadsJob()
         s.n_align, s.d_text, s.n_text = n_align, up(text), int(text.numel())
@@ -1027,15 +1012,11 @@ class HipEngine(EngineBase):
 
     def reads_last(self):
         """ms of the last fastq_scan and the last reads_pack under set_kernel_timing."""
-        ms = (ctypes.c_float * 2)()
-        self._check(self.lib.brx_reads_last(self.ctx, ctypes.byref(ms)))
-        return dict(zip(('scan', 'pack'), [float(x) for x in ms]))
+        return self._last_ms(self.lib.brx_reads_last, ('scan', 'pack'))
 
     def window_last(self):
         """ms of the kernels of the last window_means under set_kernel_timing: errors, scans, stats, values."""
-        ms = (ctypes.c_float * 4)()
-        self._check(self.lib.brx_window_last(self.ctx, ctypes.byref(ms)))
-        return dict(zip(('errors', 'scans', 'stats', 'values'), [float(x) for x in ms]))
+        return self._last_ms(self.lib.brx_window_last, ('errors', 'scans', 'stats', 'values'))
 
     def gzip_device(self, data, block_off=None):
         """brx_gzip_device: a uint8 tensor of FASTQ text on this engine's device -> a uint8 tensor (same device) holding
@@ -1061,14 +1042,10 @@ class HipEngine(EngineBase):
         # library asks for it
         cap = min(int(0.7 * n) + 200 * blocks + 4096, int(self.lib.brx_gzip_device_bound(n, nb)) + 8)
         got = ctypes.c_size_t(0)
-        for _ in range(2):
-            out = torch.empty(step(cap), dtype=torch.uint8, device=self.device)
-            rc = self.lib.brx_gzip_device(self.ctx, ctypes.c_void_p(data.data_ptr()), n, d_off, nb, ctypes.c_void_p(out.data_ptr()), out.numel(),
-                                          ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), ctypes.byref(got), self._stream())
-            if rc != E_OUTPUT:
-                break
-            cap = int(self.lib.brx_output_needed(self.ctx)) + 8
-        self._check(rc)
+        out = self._sized_call(lambda out, _, scr: self.lib.brx_gzip_device(
+            self.ctx, ctypes.c_void_p(data.data_ptr()), n, d_off, nb, ctypes.c_void_p(out.data_ptr()), out.numel(),
+            ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), ctypes.byref(got), self._stream()), 2,
+            (cap, lambda c: torch.empty(step(c), dtype=torch.uint8, device=self.device), lambda need, c: need + 8))
         return out[:got.value]
 
     def stage_ms(self):

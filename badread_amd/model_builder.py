@@ -38,6 +38,21 @@ def check_alignment_matches_read_and_refs(a, reads, refs):
         sys.exit(f'\nError: could not find reference {a.ref_name}\nare you sure your reference file and alignment file match?')
 
 
+def clipped(start, end, length):
+    """The indices x[start:end] takes of a sequence of `length` items: Python's clipping rule without the sequence."""
+    return range(*slice(start, end).indices(length))
+
+
+def cut(a, refs, reads):
+    """(read slice, its qualities, reference slice on the read's strand, M / I / D parts) of alignment a: what align_sequences
+    (alignment.py:101-132) works on; it ignores every other CIGAR letter."""
+    read_seq, read_qual = (x[a.read_start:a.read_end] for x in reads[a.read_name])
+    ref_seq = refs[a.ref_name][a.ref_start:a.ref_end]
+    if a.strand == '-':
+        ref_seq = reverse_complement(ref_seq)
+    return read_seq, read_qual, ref_seq, [(n, t) for n, t in a.cigar_parts if t in _TYPE]
+
+
 class Job(object):
     """The alignments as flat arrays (what brx_model_job points at) + the per-alignment strings for the spilled windows."""
 
@@ -49,11 +64,7 @@ class Job(object):
         self.slices = []
         for a in alignments:
             check_alignment_matches_read_and_refs(a, reads, refs)
-            read_seq, read_qual = (x[a.read_start:a.read_end] for x in reads[a.read_name])
-            ref_seq = refs[a.ref_name][a.ref_start:a.ref_end]
-            if a.strand == '-':
-                ref_seq = reverse_complement(ref_seq)
-            parts = [(n, t) for n, t in a.cigar_parts if t in _TYPE]       # align_sequences ignores every other letter
+            read_seq, read_qual, ref_seq, parts = cut(a, refs, reads)
             used_read = sum(n for n, t in parts if t != 'D')
             used_ref = sum(n for n, t in parts if t != 'I')
             if used_read > len(read_seq) or used_ref > len(ref_seq) or len(read_qual) < len(read_seq):
@@ -99,17 +110,16 @@ class Job(object):
             check_alignment_matches_read_and_refs(a, reads, refs)
             if on_device:                                   # ranges stand in for the two strings: only their lengths are asked for
                 seq_at, seq_n, qual_at, qual_n = reads.spans(a.read_name)
-                read_seq = range(*slice(a.read_start, a.read_end).indices(seq_n))
-                read_qual = range(*slice(a.read_start, a.read_end).indices(qual_n))
+                read_seq, read_qual = clipped(a.read_start, a.read_end, seq_n), clipped(a.read_start, a.read_end, qual_n)
                 seq_src[k], qual_src[k] = seq_at + read_seq.start, qual_at + read_qual.start
             else:
                 read_seq, read_qual = (x[a.read_start:a.read_end] for x in reads[a.read_name])
-            lo, hi, _ = slice(a.ref_start, a.ref_end).indices(len(refs[a.ref_name]))           # Python's clipping rule
-            if used_read[k] > len(read_seq) or used_ref[k] > max(hi - lo, 0) or len(read_qual) < len(read_seq):
+            ref_seq = clipped(a.ref_start, a.ref_end, len(refs[a.ref_name]))
+            if used_read[k] > len(read_seq) or used_ref[k] > len(ref_seq) or len(read_qual) < len(read_seq):
                 sys.exit(f'Error: the CIGAR of {a!r} runs past its read or reference range')
             if not on_device:
                 seqs.append(read_seq); quals.append(read_qual[:len(read_seq)])
-            read_len[k], ref_off[k], ref_len[k] = len(read_seq), ref_at[a.ref_name] + lo, max(hi - lo, 0)
+            read_len[k], ref_off[k], ref_len[k] = len(read_seq), ref_at[a.ref_name] + ref_seq.start, len(ref_seq)
         offsets = lambda x: np.concatenate((np.zeros(1, dtype=np.uint64), np.cumsum(x, dtype=np.uint64)))
         self.align_part_off = offsets(rec['n_parts'])
         self.align_col_off = offsets(rec['sum_m'] + rec['sum_i'] + rec['sum_d'])
@@ -159,12 +169,7 @@ class _LazySlices(object):
         return len(self.alignments)
 
     def __getitem__(self, k):
-        a = self.alignments[k]
-        read_seq, read_qual = (x[a.read_start:a.read_end] for x in self.reads[a.read_name])
-        ref_seq = self.refs[a.ref_name][a.ref_start:a.ref_end]
-        if a.strand == '-':
-            ref_seq = reverse_complement(ref_seq)
-        return read_seq, read_qual, ref_seq, [(n, t) for n, t in a.cigar_parts if t in _TYPE]
+        return cut(self.alignments[k], self.refs, self.reads)
 
 
 def _device_reference(engine, refs, packed):
@@ -191,38 +196,47 @@ def _device_complement(engine, packed):
     return held
 
 
-def _load(args, engine, output):
-    """The alignments of a model command: load_alignments, or with --gpu-loader its device twin."""
-    if getattr(args, 'gpu_loader', False):
-        return load_alignments_device(args.alignment, engine, args.max_alignments, output=output)
-    return load_alignments(args.alignment, args.max_alignments, output=output)
-
-
 def _job(engine, refs, reads, alignments):
     if isinstance(alignments, DeviceAlignments):
         return Job.packed(engine, refs, reads, alignments, 0, len(alignments))
     return Job(refs, reads, alignments)
 
 
-def _engine(args, engine):
-    """The engine before the alignments are loaded when the loader needs it, else where it always was made."""
-    if engine is None and getattr(args, 'gpu_loader', False):
+def _default_engine(engine=None):
+    """`engine`, or the process's own: the one place where a command opens the device (the driver then prints to stderr)."""
+    if engine is None:
         from .engine import default_engine
         engine = default_engine()
     return engine
 
 
-def check_gpu_reads(args):
-    if getattr(args, 'gpu_reads', False) and not getattr(args, 'gpu_loader', False):
+def load_inputs(args, engine, output, order):
+    """(refs, reads, alignments, engine) of a command, loaded in `order` ('reference', 'reads', 'alignments' in the command's own
+    sequence) with their "Loading ..." lines on `output`.  --gpu-reads / --gpu-loader take the device twins of load_fastq /
+    load_alignments, and the engine is made just before the first of them that needs it; without either flag it comes back as it
+    came (None: the caller opens the device where it starts to compute, after its own checks and exits)."""
+    gpu_loader, gpu_reads = getattr(args, 'gpu_loader', False), getattr(args, 'gpu_reads', False)
+    if gpu_reads and not gpu_loader:
         sys.exit('Error: --gpu-reads needs --gpu-loader')
+    max_alignments = getattr(args, 'max_alignments', None)
+    got = {}
+    for what in order:
+        if what == 'reference':
+            got[what] = load_fasta(args.reference)[0]
+        elif what == 'reads' and gpu_reads:
+            engine = _default_engine(engine)
+            got[what] = load_fastq_device(args.reads, engine, output=output)
+        elif what == 'reads':
+            got[what] = load_fastq(args.reads, output=output)
+        elif gpu_loader:
+            engine = _default_engine(engine)
+            got[what] = load_alignments_device(args.alignment, engine, max_alignments, output=output)
+        else:
+            got[what] = load_alignments(args.alignment, max_alignments, output=output)
+    return got['reference'], got['reads'], got['alignments'], engine
 
 
-def _reads(args, engine, output):
-    """(the reads of a model command, the engine): load_fastq, or with --gpu-reads its device twin, which needs the engine first."""
-    if getattr(args, 'gpu_reads', False):
-        engine = _engine(args, engine)
-        return load_fastq_device(args.reads, engine, output=output), engine
-    return load_fastq(args.reads, output=output), engine
+MODEL_ORDER = ('reference', 'reads', 'alignments')
 
 
 def _table(engine, kind, job, k, max_del, n_ksizes, first_bits=16):
@@ -276,19 +290,13 @@ def count_error_model(engine, job, k, first_bits=16):
 
 def make_error_model(args, output=sys.stderr, dot_interval=1000, engine=None, stdout=None):
     stdout = stdout or sys.stdout
-    check_gpu_reads(args)
-    refs, _, _, _, _ = load_fasta(args.reference)
-    reads, engine = _reads(args, engine, output)
-    engine = _engine(args, engine)
-    alignments = _load(args, engine, output)
+    refs, reads, alignments, engine = load_inputs(args, engine, output, MODEL_ORDER)
     if len(alignments) == 0:
         sys.exit('Error: no usable alignments')
     k = args.k_size
     if not 2 <= k <= 8:
         sys.exit('Error: the GPU error-model builder supports --k_size 2 to 8')
-    if engine is None:
-        from .engine import default_engine
-        engine = default_engine()
+    engine = _default_engine(engine)
     print('Processing alignments', end='', file=output, flush=True)
     found = count_error_model(engine, _job(engine, refs, reads, alignments), k)
     print('.' * (len(alignments) // dot_interval), file=output, flush=True)
@@ -360,20 +368,14 @@ def count_qscore_model(engine, job, k_size, max_del, first_bits=16):
 
 def make_qscore_model(args, output=sys.stderr, dot_interval=1000, engine=None, stdout=None):
     stdout = stdout or sys.stdout
-    check_gpu_reads(args)
-    refs, _, _, _, _ = load_fasta(args.reference)
-    reads, engine = _reads(args, engine, output)
-    engine = _engine(args, engine)
-    alignments = _load(args, engine, output)
+    refs, reads, alignments, engine = load_inputs(args, engine, output, MODEL_ORDER)
     if len(alignments) == 0:
         sys.exit('Error: no usable alignments')
     assert args.k_size % 2 == 1
     n_ksizes = (args.k_size + 1) // 2
     if n_ksizes > 16 or args.max_del > 15:
         sys.exit('Error: the GPU qscore-model builder supports --k_size up to 31 and --max_del up to 15')
-    if engine is None:
-        from .engine import default_engine
-        engine = default_engine()
+    engine = _default_engine(engine)
     print('Processing alignments', end='', file=output, flush=True)
     per_cigar = count_qscore_model(engine, _job(engine, refs, reads, alignments), args.k_size, args.max_del)
     print('.' * (len(alignments) // dot_interval), file=output, flush=True)

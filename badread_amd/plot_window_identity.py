@@ -26,10 +26,8 @@ import sys
 
 import numpy as np
 
-from .alignment import NO_D, DeviceAlignments, load_alignments, load_alignments_device
-from .misc import load_fasta, load_fastq
-from .model_builder import Job, check_alignment_matches_read_and_refs, check_gpu_reads
-from .reads import load_fastq_device
+from .alignment import NO_D, DeviceAlignments
+from .model_builder import Job, _default_engine, check_alignment_matches_read_and_refs, clipped, load_inputs
 from .reads import read_length as read_length_of
 
 PLOT_CHUNK_BASES = 1 << 26                 # read bases per device call: 20 bytes of scratch each, 28 with --qual
@@ -81,7 +79,7 @@ def _check_packed(a, rec, reads, refs, qual):
     it: the D with the most read bases in front of it is the last one in file order for '+' and, the list being read backwards, the
     first one for '-'."""
     check_alignment_matches_read_and_refs(a, reads, refs)
-    length = len(range(*slice(a.read_start, a.read_end).indices(read_length_of(reads, a.read_name))))
+    length = len(clipped(a.read_start, a.read_end, read_length_of(reads, a.read_name)))
     first_d, last_d, used_read = int(rec['first_d']), int(rec['last_d']), int(rec['sum_m']) + int(rec['sum_i'])
     if first_d != NO_D and (used_read - first_d >= length if a.strand == '-' else last_d >= length):
         sys.exit(f'Error: the CIGAR of {a!r} ends in a deletion with no read base after it')
@@ -182,30 +180,13 @@ def plot_window_identity(args, output=sys.stdout, engine=None, stdout=None):
         sys.exit('Error: --window must be at least 1')
     if summary is not None and not pathlib.Path(summary).resolve().parent.is_dir():
         sys.exit(f'Error: the directory of --summary {summary} does not exist')
-    check_gpu_reads(args)
-    if getattr(args, 'gpu_reads', False):
-        if engine is None:
-            from .engine import default_engine
-            engine = default_engine()
-        reads = load_fastq_device(args.reads, engine, output=output)
-    else:
-        reads = load_fastq(args.reads, output=output)
-    refs, _, _, _, _ = load_fasta(args.reference)
-    if getattr(args, 'gpu_loader', False):
-        if engine is None:
-            from .engine import default_engine
-            engine = default_engine()
-        alignments = load_alignments_device(args.alignment, engine, getattr(args, 'max_alignments', None), output=output)
-    else:
-        alignments = load_alignments(args.alignment, getattr(args, 'max_alignments', None), output=output)
+    refs, reads, alignments, engine = load_inputs(args, engine, output, ('reads', 'reference', 'alignments'))
     lengths = check_alignments(alignments, reads, refs, qual)
     draw = save is not None or not args.no_plot
     plt = _pyplot(save is not None) if draw else None
     if save is not None:
         os.makedirs(save, exist_ok=True)
-    if engine is None:
-        from .engine import default_engine
-        engine = default_engine()
+    engine = _default_engine(engine)
     with open(summary, 'w') if summary is not None else contextlib.nullcontext() as table:
         if summary is not None:
             table.write('#' + '\t'.join(SUMMARY_COLUMNS + (SUMMARY_QUAL_COLUMNS if qual else ())) + '\n')
