@@ -97,6 +97,12 @@ SIMULATE_OPTIONS = [
                              help='Also write the same true alignments to PATH as BAM (BGZF-compressed on the GPU): the header '
                                   'and the records of --truth-sam, in the same order, unsorted; can be combined with --truth-paf '
                                   'and --truth-sam; with --output-shards every rank writes PATH.<rank>, a complete BAM file')),
+        ('--truth-bam-sorted', dict(type=str, default=None, dest='truth_bam_sorted', metavar='PATH',
+                                    help='Also write the records of --truth-bam to PATH in coordinate order (sorted on the GPU when the '
+                                         'job has ended, unmapped records last, SO:coordinate) and their BAI index to PATH.bai: no '
+                                         'samtools sort or index needed; takes --truth-tags, --truth-cs and --truth-eqx; works alone '
+                                         'or with the other truth files; with --output-shards every rank writes PATH.<rank> and '
+                                         'PATH.<rank>.bai for its own reads')),
         ('--truth-tags', dict(type=str, default=None, dest='truth_tags', metavar='LIST',
                               help='Tags to add to the records of --truth-sam and --truth-bam, a comma-separated list of MD and SA: '
                                    'MD:Z: (mismatched and deleted reference bases) on every mapped line, SA:Z: (the read\'s other '
@@ -243,13 +249,15 @@ def check_simulate_args(args):
     """Validate and derive the fields simulate() reads (mean_frag_length, identity triple, glitch_*)."""
     if not pathlib.Path(args.reference).is_file():
         sys.exit(f'Error: {args.reference} is not a file')
-    for flag in ('truth_paf', 'truth_sam', 'truth_bam', 'truth_depth'):
+    for flag in ('truth_paf', 'truth_sam', 'truth_bam', 'truth_bam_sorted', 'truth_depth'):
         path = getattr(args, flag, None)
         if path is not None and not pathlib.Path(path).resolve().parent.is_dir():
             sys.exit(f'Error: the directory of --{flag.replace("_", "-")} {path} does not exist')
-    args.truth_tags = truth_tags_mask(getattr(args, 'truth_tags', None), getattr(args, 'truth_sam', None) or getattr(args, 'truth_bam', None))
+    # --truth-bam-sorted is a file of records like --truth-bam: the tags and the formats go into it
+    bam = getattr(args, 'truth_bam', None) or getattr(args, 'truth_bam_sorted', None)
+    args.truth_tags = truth_tags_mask(getattr(args, 'truth_tags', None), getattr(args, 'truth_sam', None) or bam)
     args.truth_fmt = truth_fmt_mask(getattr(args, 'truth_cs', None), bool(getattr(args, 'truth_eqx', False)),
-                                    any(getattr(args, flag, None) for flag in ('truth_paf', 'truth_sam', 'truth_bam')))
+                                    bool(bam) or any(getattr(args, flag, None) for flag in ('truth_paf', 'truth_sam')))
     for value, names, flag in ((args.error_model, ERROR_MODEL_NAMES, '--error_model'),
                                (args.qscore_model, QSCORE_MODEL_NAMES, '--qscore_model')):
         if value.lower() not in names and not pathlib.Path(value).is_file():

@@ -88,6 +88,7 @@ struct brx_ctx {
     float window_ms[4];                            /* the last brx_window_means under brx_set_kernel_timing: errors, scans, statistics, values */
     float loader_ms[2];                            /* the last brx_paf_scan and brx_align_pack under brx_set_kernel_timing */
     float reads_ms[2];                             /* the last brx_fastq_scan and brx_reads_pack under brx_set_kernel_timing */
+    float bamsort_ms[8];                           /* the last brx_bam_sort (four stages) and brx_bam_index (four) under brx_set_kernel_timing */
     char err[512];
 };
 

@@ -2,12 +2,13 @@
  * brx_tools.h -- the tool calls of the C-ABI: everything of include/brx.h that is not the simulate pipeline or brx_align_batch.
  * Included once, last, by brx_hip.hip, whose context and helpers (brx_ctx, fail, HIPCHK, wait_stream, pinned_regrow) it uses.
  *   brx_model_count                              brx_model.h      the counting loops of the model builders
- *   brx_gzip_device, brx_bgzf_device             brx_gzip_dev.h   gzip members / BGZF blocks
+ *   brx_gzip_device, brx_bgzf_device(_off)       brx_gzip_dev.h   gzip members / BGZF blocks
  *   brx_emit_paf / _sam / _bam / _depth          brx_paf.h, brx_sam.h, brx_bam.h, brx_depth.h   truth output of the last batch
  *   brx_depth_bedgraph                           brx_depth.h      the job's coverage as text
  *   brx_window_means                             brx_window.h     the plot command's numbers
  *   brx_paf_scan, brx_align_pack                 brx_pafin.h      the device loader
  *   brx_fastq_scan, brx_reads_pack               brx_fastqin.h    the device read loader
+ *   brx_bam_sort, brx_bam_index                  brx_bamsort.h    the truth BAM in coordinate order and its index
  * The kernel headers share brx_scan.h and nothing else.  The calls share three helpers, below: Carver (where a call keeps what in the
  * caller's scratch), Call (stream, timing marks, read-backs, waits, the two "too small" answers) and last_ms (the *_last getters).
  */
@@ -21,6 +22,7 @@
 #include "brx_window.h"
 #include "brx_pafin.h"
 #include "brx_fastqin.h"
+#include "brx_bamsort.h"
 
 /* Offsets into a scratch block that the caller allocated: every piece begins on a multiple of 256 bytes of the block's first such
    address, so bytes() asks for 256 more than the pieces take -- the caller's block may begin anywhere. */
@@ -109,7 +111,7 @@ extern "C" size_t brx_gzip_device_scratch(size_t n_bytes, uint32_t n_blocks) {
    out by hand, not by Carver: brx_gzip_device_scratch above promises callers the byte count of exactly this packing. */
 template <bool BGZF>
 static int gz_members(brx_ctx *c, const void *d_in, size_t n_bytes, const uint64_t *d_block_off, uint32_t n_blocks, void *d_out, size_t out_cap,
-                      void *d_scratch, size_t scratch_bytes, size_t *out_bytes, void *hip_stream) {
+                      void *d_scratch, size_t scratch_bytes, size_t *out_bytes, void *hip_stream, uint64_t *d_member_off = nullptr) {
     if (!c || !out_bytes || (n_bytes && (!d_in || !d_out || !d_scratch)) || (d_block_off && !n_blocks)) return BRX_E_ARG;
     *out_bytes = 0;
     if (!n_bytes) return BRX_OK;
@@ -134,6 +136,8 @@ static int gz_members(brx_ctx *c, const void *d_in, size_t n_bytes, const uint64
     if (total + 8 > out_cap) return K.need_output((size_t)total + 8, "brx_gzip_device: output buffer too small: need %llu bytes", (unsigned long long)total + 8);
     HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)((total + 7) & ~(uint64_t)3), K.st));
     hipLaunchKernelGGL((k_gz_pack<BGZF>), dim3(grid), dim3(64), 0, K.st, (const uint8_t *)d_in, (uint64_t)n_bytes, d_block_off, nb, (uint8_t *)d_out, member_off, tabs, offs, crcs);
+    /* brx_bgzf_device_off: where the members begin, as the scan left them at the head of the scratch */
+    if (d_member_off) HIPCHK(c, hipMemcpyAsync(d_member_off, member_off, ((size_t)nb + 1) * 8, hipMemcpyDeviceToDevice, K.st));
     BRX_TRY(K.sync("brx_gzip_device (pack)"));
     *out_bytes = (size_t)total;
     return BRX_OK;
@@ -148,10 +152,14 @@ extern "C" size_t brx_bgzf_device_bound(size_t n_bytes) {
     return nb * (18 + (BRX_GZ_HDR_BITS + 15 + 7) / 8 + 8) + (15 * n_bytes + 7) / 8 + nb + 16;
 }
 extern "C" size_t brx_bgzf_device_scratch(size_t n_bytes) { return brx_gzip_device_scratch(n_bytes, bgzf_blocks(n_bytes)); }
+extern "C" int brx_bgzf_device_off(brx_ctx *c, const void *d_in, size_t n_bytes, void *d_out, size_t out_cap, void *d_scratch, size_t scratch_bytes,
+                                   size_t *out_bytes, uint64_t *d_block_off, void *hip_stream) {
+    if (n_bytes > (size_t)BRX_BGZF_BLOCK * 0xFFFFFFFFull) return c ? fail(c, BRX_E_ARG, "brx_bgzf_device: input too long") : BRX_E_ARG;
+    return gz_members<true>(c, d_in, n_bytes, nullptr, 0, d_out, out_cap, d_scratch, scratch_bytes, out_bytes, hip_stream, d_block_off);
+}
 extern "C" int brx_bgzf_device(brx_ctx *c, const void *d_in, size_t n_bytes, void *d_out, size_t out_cap, void *d_scratch, size_t scratch_bytes,
                                size_t *out_bytes, void *hip_stream) {
-    if (n_bytes > (size_t)BRX_BGZF_BLOCK * 0xFFFFFFFFull) return c ? fail(c, BRX_E_ARG, "brx_bgzf_device: input too long") : BRX_E_ARG;
-    return gz_members<true>(c, d_in, n_bytes, nullptr, 0, d_out, out_cap, d_scratch, scratch_bytes, out_bytes, hip_stream);
+    return brx_bgzf_device_off(c, d_in, n_bytes, d_out, out_cap, d_scratch, scratch_bytes, out_bytes, nullptr, hip_stream);
 }
 
 /* ---- truth alignments of the last simulate batch: PAF text (brx_paf.h), SAM records (brx_sam.h), BAM records (brx_bam.h) or the
@@ -364,6 +372,217 @@ extern "C" int brx_depth_bedgraph(brx_ctx *c, const uint64_t *d_events, uint64_t
     hipLaunchKernelGGL(k_dp_lines, dim3((uint32_t)((n_points + BRX_DP_THREADS - 1) / BRX_DP_THREADS)), dim3(BRX_DP_THREADS), 0, st, line, (const uint64_t *)spare, n_points, ref.d_names, d_out);
     BRX_TRY(K.sync("brx_depth_bedgraph (text)"));
     c->depth_ms[2] = (float)(dp_now_ms() - t2);
+    *out_bytes = (size_t)total;
+    return BRX_OK;
+}
+
+/* ---- the truth BAM in coordinate order and its index (brx_bamsort.h) ---- */
+static uint32_t bs_blocks(uint64_t n) { return (uint32_t)((n + BRX_BS_THREADS - 1) / BRX_BS_THREADS); }
+/* the sort's own pieces for n keys, in every plan that sorts */
+struct BsSortPlan { size_t keys[2], pay[2], table, incl; };
+static BsSortPlan bs_sort_plan(Carver &V, uint64_t n) {
+    const uint64_t cells = 256ull * ((n + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE);
+    BsSortPlan p;
+    p.keys[0] = V.take(n * 8); p.keys[1] = V.take(n * 8); p.pay[0] = V.take(n * 4); p.pay[1] = V.take(n * 4);
+    p.table = V.take(cells * 4); p.incl = V.take(cells * 8);
+    return p;
+}
+static BsSort bs_sort_at(void *d_scratch, const BsSortPlan &p, uint64_t *sums) {
+    BsSort S;
+    for (int x = 0; x < 2; ++x) { S.keys[x] = Carver::at<uint64_t>(d_scratch, p.keys[x]); S.pay[x] = Carver::at<uint32_t>(d_scratch, p.pay[x]); }
+    S.table = Carver::at<uint32_t>(d_scratch, p.table); S.incl = Carver::at<uint64_t>(d_scratch, p.incl); S.sums = sums;
+    return S;
+}
+/* the words for the tile sums of a scan over up to `longest` elements */
+static uint64_t bs_sums_bytes(uint64_t longest) { return ((longest + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE + 1) * 8; }
+
+/* where brx_bam_sort keeps what in its scratch, for n_rec records in n_seg segments.  Sized twice: before the walk for the records that
+   brx_bam_sort_scratch assumes, after it for the count found. */
+struct BsPlan { size_t cnt, seg_incl, src, len, incl_len, sums, flags, bytes; BsSortPlan sort; };
+static BsPlan bs_plan(uint64_t n_rec, uint64_t n_seg) {
+    BsPlan p;
+    Carver V;
+    p.cnt = V.take(n_seg * 4); p.seg_incl = V.take(n_seg * 8); p.flags = V.take(256);
+    p.src = V.take(n_rec * 8); p.len = V.take(n_rec * 4); p.incl_len = V.take(n_rec * 8);
+    p.sort = bs_sort_plan(V, n_rec);
+    p.sums = V.take(bs_sums_bytes(std::max<uint64_t>(std::max<uint64_t>(n_rec, 256ull * ((n_rec + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE)), n_seg)));
+    p.bytes = V.bytes();
+    return p;
+}
+extern "C" size_t brx_bam_sort_scratch(uint64_t n_bytes, uint64_t n_seg) { return bs_plan(n_bytes / 4096 + n_seg + 64, n_seg).bytes; }
+extern "C" int brx_bamsort_last(const brx_ctx *c, float ms[8]) { return last_ms(c, &brx_ctx::bamsort_ms, ms); }
+
+extern "C" int brx_bam_sort(brx_ctx *c, const uint8_t *d_records, uint64_t n_bytes, const uint64_t *d_seg_off, uint64_t n_seg, uint32_t n_ref, uint32_t max_pos,
+                            uint8_t *d_sorted, brx_bam_rec *d_recs, uint64_t rec_cap, uint64_t *n_records, uint64_t *n_unmapped, void *d_scratch,
+                            size_t scratch_bytes, void *hip_stream) {
+    if (!c) return BRX_E_ARG;
+    if (!n_records || !n_unmapped) return fail(c, BRX_E_ARG, "brx_bam_sort: n_records or n_unmapped is NULL");
+    *n_records = 0; *n_unmapped = 0;
+    if (n_bytes == 0) return BRX_OK;
+    if (!d_records || !d_seg_off || !d_sorted || n_seg == 0) return fail(c, BRX_E_ARG, "brx_bam_sort: the records, the segment offsets or d_sorted is NULL");
+    if (n_bytes >= (1ull << 43) || n_seg >= (1ull << 32)) return fail(c, BRX_E_ARG, "brx_bam_sort: %llu bytes in %llu segments: fewer than 2^43 and 2^32 in one call", (unsigned long long)n_bytes, (unsigned long long)n_seg);
+    if (max_pos > (1u << 31)) return fail(c, BRX_E_ARG, "brx_bam_sort: max_pos %u above 2^31", max_pos);
+    BsPlan P = bs_plan(0, n_seg);
+    Call K(c, hip_stream);
+    const size_t least = brx_bam_sort_scratch(n_bytes, n_seg);
+    if (!d_scratch || scratch_bytes < least) return K.need_scratch("brx_bam_sort", d_scratch ? scratch_bytes : (size_t)0, least);
+    BRX_TRY(K.begin());
+    hipStream_t st = K.st;
+    /* cnt, seg_incl and flags lie in front of everything that is sized by the records: the same places in both plans */
+    uint32_t *cnt = Carver::at<uint32_t>(d_scratch, P.cnt), *flags = Carver::at<uint32_t>(d_scratch, P.flags);
+    uint64_t *seg_incl = Carver::at<uint64_t>(d_scratch, P.seg_incl);
+    uint64_t *first_unmapped = (uint64_t *)(flags + 2);
+    /* the tile sums of the first scan: behind the pieces of a plan without records, where the plan with them puts its record arrays */
+    uint64_t *sums0 = Carver::at<uint64_t>(d_scratch, P.sums);
+    const BsIn in = { d_records, n_bytes, d_seg_off, n_seg, n_ref, max_pos };
+    K.mark(0);
+    HIPCHK(c, hipMemsetAsync(flags, 0, 256, st));
+    hipLaunchKernelGGL((k_bs_walk<false>), dim3(bs_blocks(n_seg)), dim3(BRX_BS_THREADS), 0, st, in, cnt, (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr,
+                       (uint32_t *)nullptr, flags);
+    const DpSrcTable counts = { cnt };
+    dp_scan(st, counts, n_seg, sums0, seg_incl);
+    uint32_t bad = 0;
+    uint64_t n = 0;
+    BRX_TRY(K.read_back(&bad, flags, 4));
+    BRX_TRY(K.read_back(&n, seg_incl + (n_seg - 1), 8));
+    BRX_TRY(K.sync("brx_bam_sort (walk)"));
+    if (bad) return fail(c, BRX_E_ARG, "brx_bam_sort: the segment offsets do not ascend from 0 to n_bytes, a record chain leaves its segment, or a record's "
+                                       "block_size, refID or pos is out of range");
+    if (n >= (1ull << 32)) return fail(c, BRX_E_ARG, "brx_bam_sort: %llu records: fewer than 2^32 in one call", (unsigned long long)n);
+    if (n > rec_cap || !d_recs) return K.need_output((size_t)n, "brx_bam_sort: room for %llu records, %llu in the input", (unsigned long long)(d_recs ? rec_cap : 0), (unsigned long long)n);
+    P = bs_plan(n, n_seg);
+    if (scratch_bytes < P.bytes) {
+        char detail[48];
+        snprintf(detail, sizeof(detail), " for %llu records", (unsigned long long)n);
+        return K.need_scratch("brx_bam_sort", scratch_bytes, P.bytes, detail);
+    }
+    uint64_t *src = Carver::at<uint64_t>(d_scratch, P.src), *incl_len = Carver::at<uint64_t>(d_scratch, P.incl_len), *sums = Carver::at<uint64_t>(d_scratch, P.sums);
+    uint32_t *len = Carver::at<uint32_t>(d_scratch, P.len);
+    const BsSort S = bs_sort_at(d_scratch, P.sort, sums);
+    hipLaunchKernelGGL((k_bs_walk<true>), dim3(bs_blocks(n_seg)), dim3(BRX_BS_THREADS), 0, st, in, cnt, (const uint64_t *)seg_incl, src, S.keys[0], len, flags);
+    K.mark(1);
+    /* the digits that can vary: the bytes of max_pos - 1 in the low word, those of n_ref (the state of refID -1) in the high word */
+    uint32_t shifts[8], n_pass = 0;
+    for (uint32_t b = 0; b < 4; ++b) if (max_pos && ((max_pos - 1u) >> (8 * b)) != 0) shifts[n_pass++] = 8 * b;
+    for (uint32_t b = 0; b < 4; ++b) if ((n_ref >> (8 * b)) != 0) shifts[n_pass++] = 32 + 8 * b;
+    if (!n_pass) shifts[n_pass++] = 0;
+    const uint32_t r = bs_sort(st, S, n, shifts, n_pass);
+    const uint64_t *skey = S.keys[r];
+    const uint32_t *spay = S.pay[r];
+    uint64_t *ssrc = S.keys[r ^ 1u];                         /* the other side of the last pass has been read for the last time */
+    K.mark(2);
+    const BsSrcLen lens = { len, spay };
+    dp_scan(st, lens, n, sums, incl_len);
+    HIPCHK(c, hipMemcpyAsync(first_unmapped, &n, 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_bs_table, dim3((uint32_t)((n + 3) / 4)), dim3(BRX_BS_THREADS), 0, st, d_records, (const uint64_t *)src, spay, (const uint32_t *)len,
+                       (const uint64_t *)incl_len, skey, n, n_ref, d_recs, ssrc, first_unmapped);
+    K.mark(3);
+    const bool wide = ((uintptr_t)d_records & 3u) == 0, aligned = ((uintptr_t)d_sorted & 15u) == 0;
+    hipLaunchKernelGGL(k_bs_gather, dim3((uint32_t)((n_bytes + BRX_BS_SPAN - 1) / BRX_BS_SPAN)), dim3(BRX_BS_THREADS), 0, st, d_records, n_bytes, (const uint64_t *)incl_len,
+                       (const uint64_t *)ssrc, n, d_sorted, wide, aligned);
+    K.mark(4);
+    uint64_t first = 0;
+    BRX_TRY(K.read_back(&first, first_unmapped, 8));
+    BRX_TRY(K.sync("brx_bam_sort"));
+    for (int i = 0; i < 4; ++i) BRX_TRY(K.elapsed(&c->bamsort_ms[i], i, i + 1));
+    *n_records = n;
+    *n_unmapped = n - first;
+    return BRX_OK;
+}
+
+/* where brx_bam_index keeps what in its scratch, for n records (no more chunks than records) of n_ref contigs */
+struct BiPlan { size_t starts, maxend, cbeg, cend, hincl, head, cf, rf, winc, cbase, sums, flags, bytes; BsSortPlan sort; };
+static BiPlan bi_plan(uint64_t n, uint32_t n_ref) {
+    BiPlan p;
+    Carver V;
+    p.starts = V.take(n * 8); p.maxend = V.take(n * 8); p.cbeg = V.take(n * 8); p.cend = V.take(n * 8); p.hincl = V.take(n * 8); p.head = V.take((n + 1) * 8);
+    p.cf = V.take(((uint64_t)n_ref + 1) * 8); p.rf = V.take(((uint64_t)n_ref + 1) * 8); p.winc = V.take(((uint64_t)n_ref + 1) * 8); p.cbase = V.take(((uint64_t)n_ref + 1) * 8);
+    p.sort = bs_sort_plan(V, n);
+    p.sums = V.take(bs_sums_bytes(std::max<uint64_t>(std::max<uint64_t>(n, 256ull * ((n + BRX_DEPTH_TILE - 1) / BRX_DEPTH_TILE)), n_ref)));
+    p.flags = V.take(256);
+    p.bytes = V.bytes();
+    return p;
+}
+extern "C" size_t brx_bam_index_scratch(uint64_t n_records, uint32_t n_ref) { return bi_plan(n_records, n_ref).bytes; }
+
+extern "C" int brx_bam_index(brx_ctx *c, const brx_bam_rec *d_recs, uint64_t n, uint32_t n_ref, uint64_t n_bytes, const uint64_t *d_block_off, uint64_t n_blocks,
+                             uint64_t base, uint8_t *d_out, size_t out_cap, size_t *out_bytes, void *d_scratch, size_t scratch_bytes, void *hip_stream) {
+    if (!c) return BRX_E_ARG;
+    if (!out_bytes) return fail(c, BRX_E_ARG, "brx_bam_index: out_bytes is NULL");
+    *out_bytes = 0;
+    if (n && (!d_recs || !n_bytes)) return fail(c, BRX_E_ARG, "brx_bam_index: records without a table or without a stream");
+    if (!d_block_off) return fail(c, BRX_E_ARG, "brx_bam_index: d_block_off is NULL");
+    if (n >= (1ull << 32)) return fail(c, BRX_E_ARG, "brx_bam_index: %llu records: fewer than 2^32 in one call", (unsigned long long)n);
+    if (n_ref > 0x7FFFFFFFu) return fail(c, BRX_E_ARG, "brx_bam_index: n_ref %u", n_ref);
+    if (n_blocks != (n_bytes + BRX_BGZF_BLOCK - 1) / BRX_BGZF_BLOCK)
+        return fail(c, BRX_E_ARG, "brx_bam_index: %llu blocks for %llu bytes, one per %u", (unsigned long long)n_blocks, (unsigned long long)n_bytes, BRX_BGZF_BLOCK);
+    if (base >= (1ull << 48)) return fail(c, BRX_E_ARG, "brx_bam_index: base of 2^48 or more");
+    if ((uintptr_t)d_out & 3u) return fail(c, BRX_E_ARG, "brx_bam_index: the output buffer must be 4-byte aligned");
+    const BiPlan P = bi_plan(n, n_ref);
+    Call K(c, hip_stream);
+    if (!d_scratch || scratch_bytes < P.bytes) return K.need_scratch("brx_bam_index", d_scratch ? scratch_bytes : (size_t)0, P.bytes);
+    BRX_TRY(K.begin());
+    hipStream_t st = K.st;
+    uint64_t *starts = Carver::at<uint64_t>(d_scratch, P.starts), *M = Carver::at<uint64_t>(d_scratch, P.maxend), *cbeg = Carver::at<uint64_t>(d_scratch, P.cbeg);
+    uint64_t *cend = Carver::at<uint64_t>(d_scratch, P.cend), *hincl = Carver::at<uint64_t>(d_scratch, P.hincl), *head = Carver::at<uint64_t>(d_scratch, P.head);
+    uint64_t *cf = Carver::at<uint64_t>(d_scratch, P.cf), *rf = Carver::at<uint64_t>(d_scratch, P.rf), *winc = Carver::at<uint64_t>(d_scratch, P.winc);
+    uint64_t *cbase = Carver::at<uint64_t>(d_scratch, P.cbase), *sums = Carver::at<uint64_t>(d_scratch, P.sums);
+    uint32_t *err = Carver::at<uint32_t>(d_scratch, P.flags);
+    const BsSort S = bs_sort_at(d_scratch, P.sort, sums);
+    const BiVoff voff = { d_block_off, base };
+    K.mark(0);
+    HIPCHK(c, hipMemsetAsync(err, 0, 256, st));
+    hipLaunchKernelGGL(k_bi_check, dim3(bs_blocks(std::max<uint64_t>(n, n_blocks + 1))), dim3(BRX_BS_THREADS), 0, st, d_recs, n, n_ref, n_bytes, d_block_off, n_blocks + 1, base, err);
+    uint32_t bad = 0;
+    BRX_TRY(K.read_back(&bad, err, 4));
+    BRX_TRY(K.sync("brx_bam_index (check)"));
+    if (bad) return fail(c, BRX_E_ARG, "brx_bam_index: the table is not sorted, a refID, pos, end or offset is out of range, or the block offsets descend or reach 2^48");
+    /* chunks: from here on every record names a contig of the index or none */
+    uint64_t m = 0;
+    if (n) {
+        const BiSrcStart start = { d_recs };
+        dp_scan(st, start, n, sums, starts);
+        hipLaunchKernelGGL(k_bi_chunks, dim3(bs_blocks(n)), dim3(BRX_BS_THREADS), 0, st, start, (const uint64_t *)starts, n, n_bytes, voff, S.keys[0], cbeg, cend);
+        BRX_TRY(K.read_back(&m, starts + (n - 1), 8));
+        BRX_TRY(K.wait("brx_bam_index (chunks)"));
+    }
+    K.mark(1);
+    const uint64_t *skey = nullptr;
+    const uint32_t *spay = nullptr;
+    if (m) {
+        uint32_t shifts[6], n_pass = 0;
+        shifts[n_pass++] = 0; shifts[n_pass++] = 8;          /* the bin, then the bytes of the last contig's index */
+        for (uint32_t b = 0; b < 4; ++b) if (((n_ref - 1u) >> (8 * b)) != 0) shifts[n_pass++] = 32 + 8 * b;
+        const uint32_t r = bs_sort(st, S, m, shifts, n_pass);
+        skey = S.keys[r]; spay = S.pay[r];
+        const BiSrcHead heads = { skey };
+        dp_scan(st, heads, m, sums, hincl);
+        hipLaunchKernelGGL(k_bi_heads, dim3(bs_blocks(m)), dim3(BRX_BS_THREADS), 0, st, heads, (const uint64_t *)hincl, m, head);
+    }
+    K.mark(2);
+    hipLaunchKernelGGL(k_bi_contigs, dim3(bs_blocks((uint64_t)n_ref + 1)), dim3(BRX_BS_THREADS), 0, st, d_recs, n, skey, m, n_ref, cf, rf);
+    const BiLayout L = { cf, hincl, winc };
+    uint64_t n_win = 0, body = 0;
+    if (n_ref) {
+        if (n) { const BiSrcEnd ends = { d_recs }; bx_max_scan(st, ends, n, sums, M); }
+        const BiSrcIntv intv = { rf, M };
+        dp_scan(st, intv, n_ref, sums, winc);
+        dp_scan(st, L, n_ref, sums, cbase);
+        BRX_TRY(K.read_back(&n_win, winc + (n_ref - 1), 8));
+        BRX_TRY(K.read_back(&body, cbase + (n_ref - 1), 8));
+    }
+    K.mark(3);
+    BRX_TRY(K.wait("brx_bam_index (sizes)"));
+    const uint64_t total = 8 + body + 8;
+    if (total > out_cap || !d_out) return K.need_output((size_t)total, "brx_bam_index: output buffer too small: need %llu bytes", (unsigned long long)total);
+    hipLaunchKernelGGL(k_bi_put_contigs, dim3(bs_blocks((uint64_t)n_ref + 1)), dim3(BRX_BS_THREADS), 0, st, L, (const uint64_t *)cbase, (const uint64_t *)rf, n, n_ref, total, d_out);
+    if (n_win) hipLaunchKernelGGL(k_bi_put_windows, dim3(bs_blocks(n_win)), dim3(BRX_BS_THREADS), 0, st, L, (const uint64_t *)cbase, (const uint64_t *)rf, (const uint64_t *)M, d_recs,
+                                  n_ref, n_win, voff, d_out);
+    if (m) hipLaunchKernelGGL(k_bi_put_chunks, dim3(bs_blocks(m)), dim3(BRX_BS_THREADS), 0, st, L, (const uint64_t *)cbase, skey, spay, m, (const uint64_t *)head,
+                              (const uint64_t *)cbeg, (const uint64_t *)cend, d_out);
+    K.mark(4);
+    BRX_TRY(K.sync("brx_bam_index"));
+    for (int i = 0; i < 4; ++i) BRX_TRY(K.elapsed(&c->bamsort_ms[4 + i], i, i + 1));
     *out_bytes = (size_t)total;
     return BRX_OK;
 }

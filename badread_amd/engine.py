@@ -87,8 +87,9 @@ BAM_SHARE = 1.2
 # --truth-depth: the same for a batch's events, 16 bytes per truth record (161 008-161 766 records per 1.97-1.98 GB of FASTQ on configs[3],
 # profiles/truth_paf.md: 8.2e-5 records per byte, so 0.0013; shipped with 15 % on top)
 DEPTH_SHARE = 0.0015
-TRUTH_KINDS = ('paf', 'sam', 'bam', 'depth')      # the truth files, in the order a driver makes and ships them
-TRUTH_SHARE = dict(paf=PAF_SHARE, sam=SAM_SHARE, bam=BAM_SHARE, depth=DEPTH_SHARE)
+# 'bam_sorted' (--truth-bam-sorted): the batch's BAM records once more, as they are, with their reads' offsets in front (bam_sorted_frame)
+TRUTH_KINDS = ('paf', 'sam', 'bam', 'bam_sorted', 'depth')      # the truth files, in the order a driver makes and ships them
+TRUTH_SHARE = dict(paf=PAF_SHARE, sam=SAM_SHARE, bam=BAM_SHARE, bam_sorted=BAM_SHARE, depth=DEPTH_SHARE)
 DEPTH_TILE = 1024                      # include/brx.h: BRX_DEPTH_TILE, the events per workgroup of brx_depth_bedgraph's kernels
 # --truth-tags: what MD:Z: / SA:Z: add to a batch's SAM or BAM records, per FASTQ byte (measured 0.0574-0.0578 and 0.0097-0.0099 on
 # configs[3], the same within 0.0003 in BAM: profiles/truth_tags.md; MD grows with the error rate, and E_OUTPUT's retry is behind it)
@@ -110,7 +111,8 @@ CS_LONG_SHARE = dict(paf=0.635, sam=0.635, bam=0.635)
 
 
 def fmt_share(fmt, kind):
-    """What the format bits add to the file `kind` ('paf', 'sam' or 'bam'), per FASTQ byte."""
+    """What the format bits add to the file `kind` ('paf', 'sam' or 'bam'; 'bam_sorted' holds BAM records), per FASTQ byte."""
+    kind = 'bam' if kind == 'bam_sorted' else kind
     cs = (CS_LONG_SHARE if fmt & FMT_CS_LONG else CS_SHORT_SHARE)[kind] if fmt & FMT_CS else 0.0
     return (EQX_SHARE[kind] if fmt & FMT_EQX else 0.0) + cs
 E_SCRATCH, E_OUTPUT, E_NOFRAG = -3, -4, -5
@@ -179,6 +181,12 @@ FQ_LINES, FQ_HEADER, FQ_HIGH = 1, 2, 4
 FASTQ_REC_DTYPE = np.dtype([('head_off', '<u8'), ('name_off', '<u4'), ('name_len', '<u4'), ('seq_off', '<u8'), ('qual_off', '<u8'),
                             ('seq_len', '<u4'), ('qual_len', '<u4'), ('flags', '<u4'), ('reserved', '<u4')])
 assert FASTQ_REC_DTYPE.itemsize == 48
+
+
+# brx_bam_rec of include/brx.h: a line of the table of brx_bam_sort
+BAM_REC_DTYPE = np.dtype([('off', '<u8'), ('refID', '<i4'), ('pos', '<i4'), ('end', '<u4'), ('bin', '<u4')])
+assert BAM_REC_DTYPE.itemsize == 24
+BGZF_BLOCK = 32768                     # include/brx.h: BRX_BGZF_BLOCK, the input bytes of a block of brx_bgzf_device
 
 
 class BrxReadsJob(ctypes.Structure):
@@ -422,6 +430,22 @@ def bind_library(lib):
     lib.brx_bgzf_device.restype = ctypes.c_int
     lib.brx_bgzf_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                                     ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
+    lib.brx_bgzf_device_off.restype = ctypes.c_int
+    lib.brx_bgzf_device_off.argtypes = lib.brx_bgzf_device.argtypes[:-1] + [ctypes.c_void_p, ctypes.c_void_p]
+    lib.brx_bam_sort_scratch.restype = ctypes.c_size_t
+    lib.brx_bam_sort_scratch.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    lib.brx_bam_sort.restype = ctypes.c_int
+    lib.brx_bam_sort.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.brx_bamsort_last.restype = ctypes.c_int
+    lib.brx_bamsort_last.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float * 8)]
+    lib.brx_bam_index_scratch.restype = ctypes.c_size_t
+    lib.brx_bam_index_scratch.argtypes = [ctypes.c_uint64, ctypes.c_uint32]
+    lib.brx_bam_index.restype = ctypes.c_int
+    lib.brx_bam_index.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                  ctypes.c_uint64, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p, ctypes.c_size_t,
+                                  ctypes.c_void_p]
     lib.brx_last_mutate_passes.restype = ctypes.c_uint32
     lib.brx_last_mutate_passes.argtypes = [ctypes.c_void_p]
     lib.brx_last_final_launches.restype = ctypes.c_uint32
@@ -731,22 +755,77 @@ class HipEngine(EngineBase):
     def emit_bam_device(self, n_reads, max_cigar_ops=65535, tags=0, fmt=0):
         return self.emit_truth_device('bam', n_reads, tags, fmt, max_cigar_ops)
 
-    def bgzf_device(self, data):
+    def bgzf_device(self, data, offsets=False):
         """brx_bgzf_device: a uint8 tensor on this engine's device -> a uint8 tensor (same device) holding BGZF blocks of it, one per
-        32 KB of input.  No data, no block; the file's EOF block is the caller's (output.BGZF_EOF)."""
+        32 KB of input.  No data, no block; the file's EOF block is the caller's (output.BGZF_EOF).  `offsets` (brx_bgzf_device_off): (the
+        blocks, numpy uint64 offsets of where each begins in them, one entry more than there are blocks)."""
         torch = self.torch
         n = int(data.numel())
+        if offsets:
+            d_off = torch.zeros(-(-n // BGZF_BLOCK) + 1, dtype=torch.int64, device=self.device)
+            blocks = self._bgzf(data, n, lambda *a: self.lib.brx_bgzf_device_off(*a[:-1], ctypes.c_void_p(d_off.data_ptr()), a[-1]))
+            return blocks, d_off.cpu().numpy().view(np.uint64)
+        return self._bgzf(data, n, self.lib.brx_bgzf_device)
+
+    def _bgzf(self, data, n, entry):
+        torch = self.torch
         if n == 0:
             return torch.zeros(0, dtype=torch.uint8, device=self.device)
         step = lambda b: b if b <= (1 << 24) else -(-b // (1 << 26)) * (1 << 26)       # as gzip_device: capacities the allocator can reuse
         scratch = torch.empty(step(int(self.lib.brx_bgzf_device_scratch(n)) + 8), dtype=torch.uint8, device=self.device)
         cap = min(int(0.7 * n) + 200 * -(-n // 32768) + 4096, int(self.lib.brx_bgzf_device_bound(n)) + 8)
         got = ctypes.c_size_t(0)
-        out = self._sized_call(lambda out, _, scr: self.lib.brx_bgzf_device(
+        out = self._sized_call(lambda out, _, scr: entry(
             self.ctx, ctypes.c_void_p(data.data_ptr()), n, ctypes.c_void_p(out.data_ptr()), out.numel(),
             ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), ctypes.byref(got), self._stream()), 2,
             (cap, lambda c: torch.empty(step(c), dtype=torch.uint8, device=self.device), lambda need, c: need + 8))
         return out[:got.value]
+
+    def bam_sort(self, records, seg_off, n_ref, max_pos, cap=None):
+        """brx_bam_sort: uncompressed BAM records as a uint8 tensor on this engine's device and the offsets that cut them into segments of
+        whole records (numpy uint64: first 0, last len(records)) -> (the records ordered by ((uint32) refID, pos), stable, a uint8 tensor
+        there; their table, a uint8 tensor there holding one BAM_REC_DTYPE line per record in sorted order; the records; those of refID -1).
+        n_ref, max_pos: every record has refID in [-1, n_ref) and pos in [0, max_pos), -1 on refID -1.  `cap`: the lines of the first table
+        (default: one per 4096 bytes and one per segment); E_OUTPUT and E_SCRATCH cost one retry each."""
+        torch = self.torch
+        n = int(records.numel())
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.uint64)
+        n_seg = len(seg_off) - 1
+        if n == 0:
+            return (torch.zeros(0, dtype=torch.uint8, device=self.device),) * 2 + (0, 0)
+        d_off = torch.from_numpy(seg_off.view(np.int64).copy()).to(self.device)
+        out = torch.empty(n, dtype=torch.uint8, device=self.device)
+        cap = int(cap) if cap is not None else n // 4096 + n_seg + 64
+        got, unmapped = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        larger = lambda need, have: need if need > have else None
+        table = self._sized_call(lambda table, cap, scr: self.lib.brx_bam_sort(
+            self.ctx, ctypes.c_void_p(records.data_ptr()), n, ctypes.c_void_p(d_off.data_ptr()), n_seg, int(n_ref), int(max_pos),
+            ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(table.data_ptr()), cap, ctypes.byref(got), ctypes.byref(unmapped),
+            ctypes.c_void_p(scr.data_ptr()), scr.numel(), self._stream()), 3,
+            (cap, lambda c: torch.empty(max(c, 1) * BAM_REC_DTYPE.itemsize, dtype=torch.uint8, device=self.device), larger),
+            (int(self.lib.brx_bam_sort_scratch(n, n_seg)), lambda b: torch.empty(b, dtype=torch.uint8, device=self.device), larger))
+        return out, table[:got.value * BAM_REC_DTYPE.itemsize], int(got.value), int(unmapped.value)
+
+    def bam_index(self, table, n_ref, n_bytes, block_off, base):
+        """brx_bam_index: the table of bam_sort (a uint8 tensor on this engine's device), the length of the sorted record stream, the
+        compressed offsets of its BGZF blocks (numpy uint64, one entry more than there are blocks: bgzf_device(offsets=True), of several calls
+        put end to end) and the file offset of the first block -> the bytes of the .bai file, a uint8 tensor there."""
+        torch = self.torch
+        n = int(table.numel()) // BAM_REC_DTYPE.itemsize
+        block_off = np.ascontiguousarray(block_off, dtype=np.uint64)
+        d_off = torch.from_numpy(block_off.view(np.int64).copy()).to(self.device)
+        got = ctypes.c_size_t(0)
+        larger = lambda need, have: need if need > have else None
+        out = self._sized_call(lambda out, cap, scr: self.lib.brx_bam_index(
+            self.ctx, ctypes.c_void_p(table.data_ptr()) if n else None, n, int(n_ref), int(n_bytes), ctypes.c_void_p(d_off.data_ptr()), len(block_off) - 1,
+            int(base), ctypes.c_void_p(out.data_ptr()), cap, ctypes.byref(got), ctypes.c_void_p(scr.data_ptr()), scr.numel(), self._stream()), 3,
+            (16 + 8 * int(n_ref) + 48 * n + (1 << 12), lambda c: torch.empty(-(-c // 8) * 8, dtype=torch.uint8, device=self.device), larger),
+            (int(self.lib.brx_bam_index_scratch(n, int(n_ref))), lambda b: torch.empty(b, dtype=torch.uint8, device=self.device), larger))
+        return out[:got.value]
+
+    def bamsort_last(self):
+        """ms of the stages of the last bam_sort and the last bam_index under set_kernel_timing."""
+        return self._last_ms(self.lib.brx_bamsort_last, ('walk', 'sort', 'table', 'gather', 'chunks', 'chunk_sort', 'linear', 'text'))
 
     def depth_bedgraph(self, events, cap=None):
         """brx_depth_bedgraph: a tensor of events on this engine's device (int64 words, or their bytes as uint8: what emit_truth_device('depth')

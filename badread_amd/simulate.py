@@ -366,7 +366,9 @@ class TruthSpec(collections.namedtuple('TruthSpec', 'kinds tags fmt')):
     ('paf', 'sam', 'bam') in that order, which is the order their records are made and shipped in; `tags` (--truth-tags), TAG_MD | TAG_SA
     on the SAM and BAM records; `fmt` (--truth-eqx, --truth-cs), FMT_EQX | FMT_CS | FMT_CS_LONG on all three.  'depth' (--truth-depth), the
     last kind, is not a file of records: its batches are the records' end points, which its sink keeps until the job ends (_DepthFile);
-    tags and formats take no part in it.  TruthSpec.NONE: none."""
+    tags and formats take no part in it.  'bam_sorted' (--truth-bam-sorted) is a file of records, those of 'bam': its batches are the BAM
+    records as they are, framed with their reads' lengths (sorted_frame), which its sink keeps until the job ends (_SortedBamFile).
+    TruthSpec.NONE: none."""
     __slots__ = ()
 
     def __new__(cls, kinds=(), tags=0, fmt=0):
@@ -708,10 +710,17 @@ class _BatchPool(object):
 
     def _truth_of(self, eng, n_mine, pack):
         """{kind: (the batch's records of that kind, their read offsets, False)}; with `pack` BAM's are (the records' BGZF blocks, made at
-        once on the same stream, the read offsets into the records, True)."""
-        truth = {}
-        for kind in self.truth.kinds:
+        once on the same stream, the read offsets into the records, True).  'bam_sorted' takes the BAM records as they are: with 'bam' in
+        the job too they are emitted once."""
+        truth, kinds, raw_bam = {}, self.truth.kinds, None
+        for kind in kinds:
+            if kind == 'bam_sorted':
+                data, off = raw_bam or eng.emit_truth_device('bam', n_mine, tags=self.truth.tags, fmt=self.truth.fmt)
+                truth[kind] = (data, off, False)
+                continue
             data, off = eng.emit_truth_device(kind, n_mine, tags=self.truth.tags, fmt=self.truth.fmt)
+            if kind == 'bam' and 'bam_sorted' in kinds:
+                raw_bam = (data, off)
             packed = kind == 'bam' and pack and int(data.numel()) > 0
             truth[kind] = (eng.bgzf_device(data) if packed else data, off, packed)
         return truth
@@ -901,6 +910,9 @@ class _Run(object):
             if kind == 'bam':
                 data = self.pack_bam(part, keep)
                 nbytes = int(data.numel()) if data is not None else 0
+            elif kind == 'bam_sorted':
+                data = sorted_frame(self.torch, part, keep)
+                nbytes = int(data.numel()) if data is not None else 0
             else:
                 data, nbytes = (part[0], int(part[1][keep])) if part is not None else (None, 0)
             kind_sizes = None
@@ -1017,6 +1029,22 @@ class _Run(object):
                      'no output was written for it or any later read')
 
 
+SORTED_FRAME_MAGIC = 0x4458524244544f53      # the word a frame of --truth-bam-sorted begins with: the sink's check that it reads frames
+
+
+def sorted_frame(torch, part, keep):
+    """What a batch leaves for --truth-bam-sorted: the BAM records of this rank's first `keep` reads behind a frame of 64-bit words -- the
+    magic, the reads, the records' bytes, then every read's bytes.  The sink finds the frames one behind the other in the bytes it was
+    given, however the ring or the collection to rank 0 cut or joined them.  None: nothing to keep."""
+    if part is None or keep == 0:
+        return None
+    data, off, _ = part
+    raw = int(off[keep])
+    words = np.concatenate(([SORTED_FRAME_MAGIC, keep, raw], np.diff(off[:keep + 1].astype(np.int64)))).astype('<u8')
+    head = torch.from_numpy(words.view(np.uint8).copy()).to(data.device)
+    return torch.cat([head, data[:raw]])
+
+
 def expected_error_rate(identities):
     """Mean errors per base of the job's identity law (beta: 1 - mean; qscore-normal: E[10^(-q / 10)]): what the traceback stores of
     a batch grow with (engine.presize)."""
@@ -1062,8 +1090,9 @@ class _PartsLog(object):
 class _Outputs(object):
     """Where a rank's bytes go (open_outputs): `write` to rank 0's stdout (through --gzip's sink if asked for); with --output-shards
     `local_write` and `local_parts`, this rank's own file and parts log (None where not in use); `truth_write`, {kind: the write of this
-    rank's --truth-<kind> file}; `depth`, this rank's --truth-depth file (a _DepthFile, to be finished when the job has ended)."""
-    local_write = local_parts = depth = None
+    rank's --truth-<kind> file}; `depth`, this rank's --truth-depth file (a _DepthFile, to be finished when the job has ended);
+    `sorted_bam`, this rank's --truth-bam-sorted pair of files (a _SortedBamFile, finished the same way)."""
+    local_write = local_parts = depth = sorted_bam = None
 
     def __init__(self, sink):
         self.sink, self.files, self.bam_files, self.truth_write = sink, [], [], {}
@@ -1178,6 +1207,26 @@ def open_outputs(args, shard, engine, stdout, pref=None):
                 from .output import GzipSink
             outs.depth = _DepthFile(GzipSink(f, gzip_level if gzip_level is not None else 6) if zipped else f)
             outs.truth_write['depth'] = outs.depth.write
+    # --truth-bam-sorted PATH: the records of --truth-bam in coordinate order and PATH.bai, their index.  The sink keeps the batches' raw
+    # records (the same ring and the same cut as the other truth files) and writes both files when the job has ended (_SortedBamFile);
+    # with --output-shards every rank writes PATH.<rank> and PATH.<rank>.bai, the records of the reads of its own FASTQ file
+    path = getattr(args, 'truth_bam_sorted', None)
+    if path:
+        if not hasattr(engine, 'bam_sort'):
+            shard.finish()
+            sys.exit('Error: --truth-bam-sorted needs the GPU engine')
+        try:                                   # every rank alike: it depends on the reference alone
+            bam_header(pref, b'')
+        except ValueError as ex:
+            shard.finish()
+            sys.exit(f'Error: --truth-bam-sorted: {ex}')
+        long_ones = [str(n) for n, x in zip(pref.names, pref.lengths) if int(x) >= BAI_MAX_LENGTH]
+        if long_ones:
+            shard.finish()
+            sys.exit(f'Error: --truth-bam-sorted: contig {long_ones[0]} is too long for a BAI index')
+        if prefix or shard.rank == 0:
+            outs.sorted_bam = _SortedBamFile(f'{path}.{shard.rank}' if prefix else path, pref)
+            outs.truth_write['bam_sorted'] = outs.sorted_bam.write
     return outs
 
 
@@ -1222,11 +1271,116 @@ class _DepthFile(object):
         self.sink.write(memoryview(text.cpu().numpy()))
 
 
-def sam_header(pref):
+BAI_MAX_LENGTH = 2 ** 29                    # a BAI index has bins and windows for positions below 2^29
+SORTED_SPAN = 8192 * 32768                  # --truth-bam-sorted: bytes of the sorted stream per call of brx_bgzf_device, whole blocks
+
+
+class _SortedBamFile(object):
+    """The sink of --truth-bam-sorted.  `write` (the ring's writer thread) keeps what every batch leaves (sorted_frame): the raw BAM records
+    of the reads the FASTQ holds, in host memory, of every rank on rank 0 or with --output-shards this rank's own.  `finish`, called once
+    when the job has ended normally, uploads them, has the engine -- still open, its batches done -- sort them (brx_bam_sort), compress
+    the sorted stream in spans of whole 32 KB blocks (brx_bgzf_device_off: the blocks do not depend on the spans) and make the index
+    (brx_bam_index), and writes PATH and PATH.bai.  The records twice, their table and the scratch must fit the device then; a job that
+    does not reach `finish`, or fails in it, leaves neither file."""
+
+    def __init__(self, path, pref):
+        self.path, self.pref, self.parts = path, pref, []
+        if not os.path.isdir(os.path.dirname(os.path.abspath(path))):      # now, not when the job has run: the other truth files' error
+            raise FileNotFoundError(2, 'No such file or directory', path)
+
+    def write(self, part):
+        self.parts.append(np.frombuffer(bytearray(part), dtype=np.uint8))      # a copy: the ring's buffer is reused
+
+    def frames(self):
+        """(the bytes of every read, the pieces of records) of the frames kept, in the order they came.  The pieces are views of what
+        `write` kept -- a frame may begin in one part and end in another --, so the records lie in host memory once."""
+        parts, self.parts = self.parts, []
+        where = [0, 0]                          # the part and the byte in it that come next
+
+        def take(n):
+            got = []
+            while n:
+                part = parts[where[0]]
+                piece = part[where[1]:where[1] + n]
+                got.append(piece)
+                n -= len(piece)
+                where[1] += len(piece)
+                if where[1] == len(part):
+                    where[:] = [where[0] + 1, 0]
+            return got
+        lens, pieces = [], []
+        while where[0] < len(parts):
+            if not len(parts[where[0]]):
+                where[0] += 1
+                continue
+            magic, keep, raw = (int(x) for x in np.concatenate(take(24)).view('<u8'))
+            assert magic == SORTED_FRAME_MAGIC, 'a frame of --truth-bam-sorted was expected here'
+            lens.append(np.concatenate(take(8 * keep)).view('<u8'))
+            pieces += take(raw)
+        return (np.concatenate(lens) if lens else np.zeros(0, dtype=np.uint64)), pieces
+
+    def finish(self, engine):
+        from .output import BGZF_EOF, bam_header, bgzf_host
+        torch = engine.torch
+        lens, pieces = self.frames()
+        seg_off = np.concatenate(([0], np.cumsum(lens, dtype=np.uint64))).astype(np.uint64)
+        n_bytes, n_ref = int(seg_off[-1]), len(self.pref.names)
+        need = 2 * n_bytes + int(engine.lib.brx_bam_sort_scratch(n_bytes, len(lens))) + 24 * (n_bytes // 4096 + len(lens) + 64)
+        done = []
+        try:
+            try:
+                if getattr(engine.device, 'type', 'cpu') == 'cuda':
+                    torch.cuda.empty_cache()        # the batches' buffers, back to the driver
+                    if need > torch.cuda.mem_get_info(engine.device)[0]:
+                        raise MemoryError
+                records = torch.empty(n_bytes, dtype=torch.uint8, device=engine.device)
+                at = 0
+                for piece in pieces:
+                    records[at:at + len(piece)].copy_(torch.from_numpy(piece))
+                    at += len(piece)
+                ordered, table, n, unmapped = engine.bam_sort(records, seg_off, n_ref, max([int(x) for x in self.pref.lengths] + [1]))
+                del records
+            except (MemoryError, getattr(torch, 'OutOfMemoryError', MemoryError)):
+                n = sum(_count_records(piece) for piece in pieces)
+                sys.exit(f'Error: --truth-bam-sorted: {n} records ({n_bytes / 1e9:.1f} GB) need {need / 1e9:.1f} GB on the device')
+            del pieces
+            head = bgzf_host(bam_header(self.pref, text=sam_header(self.pref, 'SO:coordinate')))
+            block_off, total = [], 0
+            done.append(self.path)
+            with open(self.path, 'wb') as f:
+                f.write(head)
+                for a in range(0, n_bytes, SORTED_SPAN):
+                    blocks, off = engine.bgzf_device(ordered[a:a + SORTED_SPAN], offsets=True)
+                    f.write(memoryview(blocks.cpu().numpy()))
+                    block_off.append(off[:-1] + np.uint64(total))
+                    total += int(off[-1])
+                f.write(BGZF_EOF)
+            block_off = np.concatenate(block_off + [np.array([total], dtype=np.uint64)])
+            index = engine.bam_index(table, n_ref, n_bytes, block_off, len(head))
+            done.append(self.path + '.bai')
+            with open(self.path + '.bai', 'wb') as f:
+                f.write(memoryview(index.cpu().numpy()))
+        except BaseException:
+            for name in done:                   # neither file, not a part of one
+                with contextlib.suppress(OSError):
+                    os.remove(name)
+            raise
+
+
+def _count_records(piece):
+    """The BAM records of a piece of whole records, by their block_size chain (the error path of _SortedBamFile.finish only)."""
+    n, at = 0, 0
+    while at + 4 <= len(piece):
+        at += 4 + int(piece[at:at + 4].view('<u4')[0])
+        n += 1
+    return n
+
+
+def sam_header(pref, order='SO:unsorted\tGO:query'):
     """The @ lines of a --truth-sam file: the contigs in reference order under the names the records use.  No CL: field and nothing
-    else of the run: the file does not depend on streams, batch sizes or ranks."""
+    else of the run: the file does not depend on streams, batch sizes or ranks.  `order`: what @HD says of the records' order."""
     from .version import __version__
-    lines = ['@HD\tVN:1.6\tSO:unsorted\tGO:query']
+    lines = ['@HD\tVN:1.6\t' + order]
     lines += [f'@SQ\tSN:{name}\tLN:{int(length)}' for name, length in zip(pref.names, pref.lengths)]
     lines.append(f'@PG\tID:badread_amd\tPN:badread_amd\tVN:{__version__}')
     return ('\n'.join(lines) + '\n').encode()
@@ -1296,6 +1450,10 @@ def simulate(args, output=sys.stderr, engine=None, stdout=None, shard=None):
                                  arenas=arenas, truth=truth, truth_write=outs.truth_write)
             if outs.depth is not None:      # the job has ended normally: the coverage of the events it kept, on the engine that is still open
                 outs.depth.finish(engine)
+            if outs.sorted_bam is not None:  # the same for the records --truth-bam-sorted kept
+                t_sorted = time.perf_counter()
+                outs.sorted_bam.finish(engine)
+                run_batches.last_timing['truth_bam_sorted_finish'] = time.perf_counter() - t_sorted
         finally:
             outs.close()
     except (SystemExit, OSError):

@@ -620,6 +620,66 @@ size_t brx_bgzf_device_bound(size_t n_bytes);
 size_t brx_bgzf_device_scratch(size_t n_bytes);
 int brx_bgzf_device(brx_ctx *ctx, const void *d_in, size_t n_bytes, void *d_out, size_t out_cap, void *d_scratch, size_t scratch_bytes,
                     size_t *out_bytes, void *hip_stream);
+/* brx_bgzf_device with one more output: d_block_off (device memory, may be NULL: exactly the call above) receives n_blocks + 1 offsets,
+ * n_blocks = ceil(n_bytes / BRX_BGZF_BLOCK): where each block begins in d_out, the last entry = *out_bytes.  The blocks' bytes are those
+ * of brx_bgzf_device.  Nothing is written to it when the call answers BRX_E_OUTPUT or BRX_E_SCRATCH, and nothing for n_bytes = 0. */
+int brx_bgzf_device_off(brx_ctx *ctx, const void *d_in, size_t n_bytes, void *d_out, size_t out_cap, void *d_scratch, size_t scratch_bytes,
+                        size_t *out_bytes, uint64_t *d_block_off, void *hip_stream);
+
+/* ---- the truth BAM in coordinate order and its index (README: --truth-bam-sorted) ----
+ * brx_bam_sort: n_bytes of uncompressed BAM records back to back (device memory; what brx_emit_bam writes, of any number of batches)
+ * and d_seg_off, n_seg + 1 ascending offsets (first 0, last n_bytes) that cut them into segments of whole records -- reads are the intended
+ * segments, a segment may be empty -> the same records in d_sorted (n_bytes, device memory) ordered by ((uint32_t)refID, pos), so that
+ * refID -1 comes last.  The sort is stable: equal keys keep the order of the input.  d_recs receives one brx_bam_rec per record in sorted
+ * order: off = where the record begins in d_sorted, refID, pos and bin as the record holds them, end = pos + reflen, reflen = the sum of the
+ * M, D, N, = and X lengths of the CIGAR field (of a long-CIGAR record: the N of its placeholder), 0 counting as 1; end = 0 on refID -1.
+ * *n_records = the records, *n_unmapped = those of refID -1.  n_ref and max_pos say what the keys can hold: a record needs refID in
+ * [-1, n_ref), pos in [0, max_pos) and, on refID -1, pos -1; only the digits that n_ref and max_pos let vary are sorted by.
+ * Every record is walked by its block_size first, inside its segment: a chain that leaves its segment or does not end on the segment's
+ * end, a block_size below 32 + l_read_name + 4 n_cigar_op, a refID or pos outside the ranges above are refused before any byte is moved.
+ *   BRX_E_ARG                            a NULL argument that is needed; offsets that do not begin at 0, ascend and end at n_bytes; a record
+ *                                        refused as above; 2^32 or more records; 2^43 or more bytes; max_pos above 2^31.  Nothing written.
+ *   BRX_E_OUTPUT + brx_output_needed()   rec_cap is below the number of records (needed: the records); nothing written.
+ *   BRX_E_SCRATCH + brx_scratch_needed() scratch_bytes is too small.  brx_bam_sort_scratch(n_bytes, n_seg) is enough for one record per
+ *                                        4096 bytes and one per segment; input with more records needs more, and the call names the size.
+ * Zero bytes is a valid call (no record).  LSD radix sort of (key, record number), 8 bits per pass, over tiles of BRX_DEPTH_TILE keys; the
+ * gather is gridded over the output, every byte of d_sorted has one writer.  No global atomics, no waiting between workgroups.  Synchronous
+ * on `hip_stream`; takes nothing from the simulate pipeline's state.
+ * brx_bamsort_last: ms between HIP events of the last brx_bam_sort on ctx that ran under brx_set_kernel_timing (walk and table of records,
+ * sort, length scan and record table, gather) and of the last brx_bam_index (check and chunks, chunk sort, linear index, text). */
+typedef struct {
+    uint64_t off;
+    int32_t refID, pos;
+    uint32_t end, bin;
+} brx_bam_rec;
+size_t brx_bam_sort_scratch(uint64_t n_bytes, uint64_t n_seg);
+int brx_bam_sort(brx_ctx *ctx, const uint8_t *d_records, uint64_t n_bytes, const uint64_t *d_seg_off, uint64_t n_seg, uint32_t n_ref,
+                 uint32_t max_pos, uint8_t *d_sorted, brx_bam_rec *d_recs, uint64_t rec_cap, uint64_t *n_records, uint64_t *n_unmapped,
+                 void *d_scratch, size_t scratch_bytes, void *hip_stream);
+int brx_bamsort_last(const brx_ctx *ctx, float ms[8]);
+
+/* brx_bam_index: the BAI index (SAM spec v1 section 5.2, without the metadata pseudo-bin) of a sorted record stream of n_bytes that was
+ * compressed into BGZF blocks of BRX_BGZF_BLOCK input bytes.  d_recs: the table brx_bam_sort wrote, n_records lines.  d_block_off:
+ * n_blocks + 1 ascending compressed offsets of the blocks, n_blocks = ceil(n_bytes / BRX_BGZF_BLOCK), the last entry = where the file's
+ * EOF block begins; `base` = the file offset of block 0 (the compressed header), added to each.  The byte at offset u of the stream has the
+ * virtual offset (base + d_block_off[u / 32768]) << 16 | u % 32768.  d_out (4-byte aligned) receives, all little-endian:
+ *   "BAI\1", int32 n_ref; per contig: int32 n_bin, the bins in ascending number {uint32 bin, int32 n_chunk, n_chunk x {uint64 beg, end}},
+ *   int32 n_intv, n_intv x uint64 ioffset; uint64 n_no_coor = the records of refID -1.
+ * A chunk is a maximal run of records consecutive in the file, of one contig and one bin: beg = the virtual offset of its first record, end
+ * = that of the byte behind its last; a bin's chunks in file order, none merged.  n_intv = (the contig's largest end - 1 >> 14) + 1;
+ * ioffset[w] = the virtual offset of the first record in file order with pos < (w + 1) << 14 and end > w << 14; a window no record
+ * overlaps takes the value of the next window that has one; a contig without records has n_bin 0 and n_intv 0.
+ *   BRX_E_ARG                            a NULL argument that is needed; the table is not sorted by ((uint32_t)refID, pos) or its offsets do
+ *                                        not ascend inside [0, n_bytes); a refID outside [-1, n_ref); a mapped record with pos < 0, end <=
+ *                                        pos or end > 2^29; n_blocks other than ceil(n_bytes / 32768); block offsets that descend or reach
+ *                                        2^48 with base; 2^32 or more records.  Nothing written.
+ *   BRX_E_OUTPUT + brx_output_needed()   out_cap is too small; nothing written.
+ *   BRX_E_SCRATCH + brx_scratch_needed() scratch_bytes is below brx_bam_index_scratch(n_records, n_ref).
+ * No records is a valid call.  No global atomics, no waiting between workgroups.  Synchronous on `hip_stream`. */
+size_t brx_bam_index_scratch(uint64_t n_records, uint32_t n_ref);
+int brx_bam_index(brx_ctx *ctx, const brx_bam_rec *d_recs, uint64_t n_records, uint32_t n_ref, uint64_t n_bytes, const uint64_t *d_block_off,
+                  uint64_t n_blocks, uint64_t base, uint8_t *d_out, size_t out_cap, size_t *out_bytes, void *d_scratch, size_t scratch_bytes,
+                  void *hip_stream);
 
 #ifdef __cplusplus
 }
